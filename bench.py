@@ -15,9 +15,16 @@ GPU).  Every rank encodes its own shard of Blocks on its own GPU (no data-path c
 encoded Blocks are gathered to rank 0 over RCCL (send/recv of variable-length byte tensors + the 16-byte
 Index records) and rank 0 frames the Stream.  The gather is inside the timed region.
 --scaling strong (default): --size-mib in total, whole Blocks dealt to the ranks in order (the metric's 4 GiB
-at 1/2/4/8 GPUs); --scaling weak: --size-mib per GPU.  Prints ONE JSON line on rank 0, with `roofline`,
-`cpu_baseline` (reference liblzma -T0 on the host cores, bounded wall time) and `host_to_host` (the same
-job through lzma_code on host buffers, PCIe inclusive).
+at 1/2/4/8 GPUs); --scaling weak: --size-mib per GPU.  Prints ONE JSON line on rank 0 with `roofline` and
+the stage times of the last step.
+
+A plain run only sets up, warms up, times --steps steps and prints the line.  --full adds what the headline
+figure does not need: the ratio against the reference encoder and the round trips through the reference and
+device decoders, `cpu_baseline` (reference liblzma -T0 on the host cores, bounded wall time), `host_to_host`
+(the same job through lzma_code on host buffers, PCIe inclusive), BASELINE's other single-GPU configurations
+as child runs (`configs`) and, with more than one GPU, one pass of the other scaling mode (`other_scaling`).
+--dump-outputs DIR writes what the last timed step returned (a seeded sample of the .xz Stream, its length
+and, on one GPU, the Block table) as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -278,7 +285,7 @@ def extra_configs():
     }
     out = {}
     for name, extra in runs.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-extra-configs", "--no-cpu-baseline"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-extra-configs", "--no-cpu-baseline"] + extra
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
@@ -298,15 +305,38 @@ def extra_configs():
                 "host_to_host_roundtrip_whole_output": (h2h.get("roundtrip_reference_decoder_whole_output") or {}).get("ok"),
                 "roofline": d.get("roofline"), "stage_ms_last_step": d.get("stage_ms_last_step"),
                 "wall_s": round(time.perf_counter() - t0, 1),
-                "cmd": "python bench.py " + " ".join(extra),
+                "cmd": "python bench.py --full " + " ".join(extra),
             }
         except Exception as e:  # noqa: BLE001
             out[name] = {"value": None, "error": str(e)}
     return out
 
 
+DUMP_SAMPLE = 4 << 20     # Stream bytes dumped at most: 4M x (float32 value + float64 position) = 48 MiB
+
+
+def dump_outputs(path, stream, binfo):
+    """What the last timed step returned, as float .npy files under `path`: `stream_bytes` (the Stream's length),
+    `stream_sample` (its bytes at `stream_sample_pos`: all of them up to DUMP_SAMPLE bytes, else a sample at positions
+    drawn by a fixed seed, a function of the length only) and, when given, `blocks` (one row per Block: unpadded size,
+    uncompressed size, offset in the output, total size)."""
+    os.makedirs(path, exist_ok=True)
+    n = int(stream.numel())
+    if n <= DUMP_SAMPLE:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(20261016).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    vals = stream[torch.from_numpy(pos).to(stream.device)].cpu().numpy()
+    np.save(os.path.join(path, "stream_bytes.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(path, "stream_sample_pos.npy"), pos.astype(np.float64))
+    np.save(os.path.join(path, "stream_sample.npy"), vals.astype(np.float32))
+    if binfo is not None:
+        rows = [(b.unpadded_size, b.uncompressed_size, b.out_offset, b.total_size) for b in binfo]
+        np.save(os.path.join(path, "blocks.npy"), np.array(rows, dtype=np.float64).reshape(-1, 4))
+
+
 def ref_size_child(size_mib, preset, block_size, threads):
-    """Child of the default run (`--ref-size-child`): the reference MT encoder over the WHOLE headline input (the same
+    """Child of a --full run (`--ref-size-child`): the reference MT encoder over the WHOLE headline input (the same
     seeded corpus) on `threads` host threads at low priority, while the parent's other child runs keep the GPU busy;
     prints {"ref_bytes", "seconds", "threads"}.  No GPU, no torch."""
     import ctypes as C
@@ -366,9 +396,15 @@ def main():
     ap.add_argument("--no-host-to-host", action="store_true")
     ap.add_argument("--bcj", action="store_true", help="chain {x86 BCJ, LZMA2} (SURVEY.md 8d config C5)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="the default 1-GPU run also runs BASELINE's other single-GPU configurations (C2: preset 1, 1 GiB text, "
-                         "16 MiB Blocks; C5_1gpu: 9e + x86 BCJ, 8 GiB ELF) as child processes and embeds their results as `configs`; "
-                         "this switch leaves them out")
+                    help="a --full run of the default 1-GPU workload also runs BASELINE's other single-GPU configurations (C2: preset 1, "
+                         "1 GiB text, 16 MiB Blocks; C5_1gpu: 9e + x86 BCJ, 8 GiB ELF) as child processes and embeds their results as "
+                         "`configs`; this switch leaves them out")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: ratio vs the reference and round trips, "
+                         "host_to_host, cpu_baseline, BASELINE's other configurations, the other scaling mode (the --no-* switches "
+                         "leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--ratio-async", action="store_true",
                     help="start the reference encoder of the ratio sample on the host cores BEFORE the warm-up and collect it after "
                          "the timed steps (the child runs of `configs`: a 192 MiB Block at 9e costs liblzma two minutes on one "
@@ -384,6 +420,10 @@ def main():
                          "objects present on the box, concatenated and cycled (config C5's input); tar: ustar stream "
                          "of the box's source trees, cycled with a per-cycle perturbation (config C4's input)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:
+        args.no_ratio = args.no_cpu_baseline = args.no_host_to_host = args.no_extra_configs = True
 
     if args.ref_size_child:
         o_ = xz_amd.preset_options(args.preset)
@@ -500,8 +540,10 @@ def main():
         elapsed = float(tmax.item())
 
     st = enc.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, binfo if world == 1 else None)
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         # one pass of the OTHER scaling mode (report both: the metric's strong form and config 4's weak form)
         o_mode = "weak" if args.scaling == "strong" else "strong"
         if o_mode == "strong":

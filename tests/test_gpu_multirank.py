@@ -75,7 +75,7 @@ def test_bench_two_ranks_oversubscribed():
     import subprocess
     env = dict(os.environ, XZAMD_BENCH_OVERSUBSCRIBE="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size-mib", "256", "--steps", "1",
-                        "--warmup", "1", "--no-ratio", "--no-cpu-baseline", "--no-host-to-host"],
+                        "--warmup", "1", "--full", "--no-ratio", "--no-cpu-baseline", "--no-host-to-host"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

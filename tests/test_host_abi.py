@@ -116,40 +116,12 @@ def test_preload_library_exports_the_interposed_symbols():
         assert hasattr(L, sym), sym
 
 
-REF_API = "/root/reference/src/liblzma/api"
+# What the real liblzma 5.8.3 <lzma.h> gives, recorded once under tests/golden/ (numbers only: layouts, enum values and
+# the liblzma symbols a client of examples/compress_mt.c references), so the ABI restatement is checked on every machine.
+LAYOUT_GOLDEN = os.path.join(ROOT, "tests", "golden", "lzma_h_layout.txt")
+CLIENT_SYMBOLS_GOLDEN = os.path.join(ROOT, "tests", "golden", "compress_mt_lzma_symbols.txt")
 
-
-def _real_header_dir():
-    """The REAL liblzma headers: the reference tree's (dev container) or the system's liblzma-dev."""
-    if os.path.exists(os.path.join(REF_API, "lzma.h")):
-        return REF_API
-    if os.path.exists("/usr/include/lzma.h"):
-        return "/usr/include"
-    return None
-
-
-def test_client_compiles_against_the_real_lzma_h_and_links(tmp_path, product_lib):
-    """examples/compress_mt.c compiled against the real <lzma.h> (no -DUSE_XZ_AMD) and linked against
-    libxz_amd.so only: every liblzma symbol it uses must come from the drop-in library."""
-    inc = _real_header_dir()
-    if inc is None:
-        pytest.skip("no real lzma.h on this box")
-    exe = str(tmp_path / "compress_mt_real")
-    subprocess.run(["gcc", "-O2", "-I" + inc, os.path.join(ROOT, "examples", "compress_mt.c"), "-o", exe,
-                    "-L" + os.path.join(ROOT, "xz_amd"), "-lxz_amd", "-Wl,-rpath," + os.path.join(ROOT, "xz_amd"),
-                    "-Wl,--no-undefined"], check=True)
-    undefined = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True).stdout
-    assert "lzma_stream_encoder_mt" in undefined and "lzma_code" in undefined
-
-
-def test_struct_layouts_equal_the_real_headers(tmp_path):
-    """sizeof / offsetof of every struct that crosses the boundary, compiled once against the real <lzma.h>
-    and once against include/xz_amd_lzma.h: must be identical (catches drift of the ABI restatement)."""
-    inc = _real_header_dir()
-    if inc is None:
-        pytest.skip("no real lzma.h on this box")
-    src = tmp_path / "probe.c"
-    src.write_text(r'''
+LAYOUT_PROBE = r'''
 #ifdef USE_XZ_AMD
 #include "xz_amd_lzma.h"
 #else
@@ -178,13 +150,46 @@ int main(void)
     printf("ids %llx %llx\n", (unsigned long long)LZMA_FILTER_LZMA2, (unsigned long long)LZMA_FILTER_X86);
     return 0;
 }
-''')
-    outs = []
-    for flags in (["-I" + inc], ["-DUSE_XZ_AMD", "-I" + os.path.join(ROOT, "include")]):
-        exe = str(tmp_path / ("probe" + str(len(outs))))
-        subprocess.run(["gcc", "-O1", *flags, str(src), "-o", exe], check=True)
-        outs.append(subprocess.run([exe], capture_output=True, text=True, check=True).stdout)
-    assert outs[0] == outs[1], "\n".join(l for l in outs[0].splitlines() if l not in outs[1].splitlines())
+'''
+
+
+def _golden_lines(path):
+    return [l for l in open(path).read().splitlines() if l and not l.startswith("#")]
+
+
+def _lzma_h_as_restated(tmp_path):
+    """An include directory whose <lzma.h> is include/xz_amd_lzma.h: a client that includes <lzma.h> gets the restatement."""
+    d = tmp_path / "lzma_h"
+    d.mkdir(exist_ok=True)
+    (d / "lzma.h").write_text('#include "xz_amd_lzma.h"\n')
+    return ["-I" + str(d), "-I" + os.path.join(ROOT, "include")]
+
+
+def test_client_compiles_against_the_real_lzma_h_and_links(tmp_path, product_lib):
+    """examples/compress_mt.c compiled as a liblzma client (#include <lzma.h>, no -DUSE_XZ_AMD) and linked against
+    libxz_amd.so only: every liblzma symbol it uses must come from the drop-in library, and they must be the symbols
+    (names and versions) the same client references when compiled against the real <lzma.h> (tests/golden/)."""
+    exe = str(tmp_path / "compress_mt_client")
+    subprocess.run(["gcc", "-O2", *_lzma_h_as_restated(tmp_path), os.path.join(ROOT, "examples", "compress_mt.c"), "-o", exe,
+                    "-L" + os.path.join(ROOT, "xz_amd"), "-lxz_amd", "-Wl,-rpath," + os.path.join(ROOT, "xz_amd"),
+                    "-Wl,--no-undefined"], check=True)
+    undefined = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True).stdout
+    assert "lzma_stream_encoder_mt" in undefined and "lzma_code" in undefined
+    got = sorted(l.split()[-1] for l in undefined.splitlines() if l.split() and l.split()[-1].startswith("lzma_"))
+    assert got == sorted(_golden_lines(CLIENT_SYMBOLS_GOLDEN))
+
+
+def test_struct_layouts_equal_the_real_headers(tmp_path):
+    """sizeof / offsetof of every struct that crosses the boundary, enum values and filter ids, compiled against
+    include/xz_amd_lzma.h: must be identical to the same probe compiled against the real <lzma.h> (recorded in
+    tests/golden/lzma_h_layout.txt; catches drift of the ABI restatement)."""
+    src = tmp_path / "probe.c"
+    src.write_text(LAYOUT_PROBE)
+    exe = str(tmp_path / "probe")
+    subprocess.run(["gcc", "-O1", "-DUSE_XZ_AMD", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()
+    want = _golden_lines(LAYOUT_GOLDEN)
+    assert out == want, "\n".join(l for l in want if l not in out)
 
 
 def test_mt_block_size_of_filter_chains(product_lib):

@@ -230,11 +230,15 @@ int xzamd_stream_encode_device(xzamd_ctx *ctx,
 		void *stream);
 
 /* Device .xz decoder (the reference's stream_decoder_mt.c / lzma2_decoder.c / lzma_decoder.c path, SURVEY.md
- * 8f.3): decode a single-Stream .xz file resident in device memory (filter chain {LZMA2}; checks none / CRC32 /
- * CRC64 / SHA-256 are verified, any other Check id is XZAMD_UNSUPPORTED_CHECK) into d_out.  Blocks decode in parallel, one wavefront each.  With d_expected (the original
+ * 8f.3): decode a single-Stream .xz file resident in device memory into d_out.  Filter chains, per Block: {LZMA2} and
+ * {up to three of: delta (0x03) | x86, PowerPC, IA-64, ARM, ARM-Thumb, SPARC, ARM64, RISC-V BCJ (0x04 .. 0x0B), LZMA2};
+ * declined with XZAMD_OPTIONS_ERROR: a BCJ start offset other than 0, any other filter id, any chain the reference's
+ * lzma_validate_chain refuses.  A Stream with a filtered Block needs one or two temporaries of the uncompressed size.
+ * Checks none / CRC32 / CRC64 / SHA-256 are verified, any other Check id is XZAMD_UNSUPPORTED_CHECK.  Blocks decode in parallel, one wavefront each.  With d_expected (the original
  * data, device memory, expected_size bytes: a Stream of another uncompressed size is XZAMD_DATA_ERROR) it is a VERIFICATION decode: every chunk chain that starts with a state
  * reset + properties (our spans) is its own unit, history is read from d_expected, and the decoded bytes are
- * compared with it afterwards (*mismatches).  Returns XZAMD_OK, 7 (LZMA_FORMAT_ERROR: not an .xz Stream),
+ * compared with it afterwards (*mismatches).  For a filtered Stream the history is the filtered original (made with the
+ * encoder's forward kernels when the Blocks are equally long but the last and share one chain; otherwise unit = Block).  Returns XZAMD_OK, 7 (LZMA_FORMAT_ERROR: not an .xz Stream),
  * XZAMD_OPTIONS_ERROR (unsupported chain), XZAMD_DATA_ERROR (corrupt / mismatch), XZAMD_BUF_ERROR (out_cap). */
 int xzamd_stream_decode_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, void *d_out, uint64_t out_cap,
 		uint64_t *out_size, const void *d_expected, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks,

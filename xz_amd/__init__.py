@@ -223,7 +223,8 @@ class Encoder:
         return out[: out_size.value], list(binfo)[: nb.value]
 
     def decode(self, xz, out_cap, expected=None):
-        """Decode an .xz Stream held in a CUDA uint8 tensor on the device.  With `expected` (CUDA uint8 tensor of
+        """Decode an .xz Stream held in a CUDA uint8 tensor on the device: the chains {LZMA2} and {up to three of BCJ |
+        delta, LZMA2} (a BCJ filter with a non-zero start offset is declined).  With `expected` (CUDA uint8 tensor of
         the original data) it is a span-parallel verification decode.  Returns (decoded tensor view, nblocks)."""
         import torch
         assert xz.is_cuda and xz.dtype == torch.uint8 and xz.is_contiguous()
@@ -243,6 +244,16 @@ class Encoder:
         return out[: osz.value], nb.value
 
     # debug hooks used by the parity tests
+    @staticmethod
+    def debug_decode_counters():
+        """Process-wide counts of the device decoder (test instrumentation): (temporary buffers allocated for inverse
+        filters, inverse-stage calls, forward-filter launches of verification decodes)."""
+        a = (C.c_uint64 * 3)()
+        f = lib().xzamd_debug_decode_counters_        # bound here: an older library (XZ_AMD_LIB, A/B runs) lacks it
+        f.restype, f.argtypes = None, [C.POINTER(C.c_uint64)]
+        f(a)
+        return tuple(a)
+
     def debug_fetch(self, what, count, dtype="uint32"):
         """Copy a work buffer of the last batch to the host: 1 = suffix order, 2 = position -> slot,
         3 = match-list records (8 x u32 per position), 4 = their u16 lengths."""

@@ -232,6 +232,33 @@ int xzk_dec_units(const uint8_t *d_xz, const xzamd_dec_block *d_blocks, uint32_t
 		uint16_t *d_lit_pool, uint32_t waves, uint32_t *d_counter, uint32_t *d_block_err, void *stream);
 int xzk_dec_compare(const uint8_t *a, const uint8_t *b, uint64_t n, unsigned long long *d_mismatches, void *stream);
 
+/* ---- inverse filters of the Block decoder (lzma_decode.hip) ----
+ * The filters in front of LZMA2 of one Block, in the order of its Block Header: f[i] = filter id | parameter << 8
+ * (delta, id 3: parameter = distance - 1; BCJ ids 4 .. 0x0B: none) -- the values xzamd_lzma_options.bcj carries. */
+#define XZAMD_DEC_FILTERS_MAX 3u
+typedef struct {
+	uint32_t n;                          /* 0 = the chain {LZMA2} */
+	uint32_t f[XZAMD_DEC_FILTERS_MAX];
+} xzamd_dec_chain;
+#define XZAMD_UNF_TILE 16384u           /* bytes of a Block one workgroup (BCJ, copy) or one wavefront (delta) handles */
+#define XZAMD_UNF_ROW 256u              /* bytes per tile of the delta scan's tile vectors (one byte per residue class) */
+/* One inverse stage.  Stage k undoes filter f[n - 1 - k] of every Block that has one (n > k); a Block with n = 0 takes part
+ * in stage 0 as a plain copy when tile_first gives it tiles (Streams that mix filtered and unfiltered Blocks).  The LZMA2
+ * stage of such a Stream decodes into t0; stage k reads t0 (k even) or t1 (k odd) and writes the other one, the last
+ * stage of a Block writes out -- all at the Block's upos.  Never in place. */
+typedef struct {
+	const xzamd_dec_block *blocks;
+	const xzamd_dec_chain *chains;
+	const uint32_t *tile_first;         /* nblocks + 1: exclusive prefix sum of the tiles of this stage */
+	uint32_t nblocks, stage;
+	uint8_t *t0, *t1, *out;
+	uint8_t *tile_sum, *tile_carry;     /* delta only: XZAMD_UNF_ROW bytes per tile each */
+} xzamd_unf_args;
+#define XZAMD_UNF_COPY 1u               /* some Block of the stage is not delta: dst = src first (the BCJ kernels only patch) */
+#define XZAMD_UNF_BCJ 2u
+#define XZAMD_UNF_DELTA 4u
+int xzk_dec_unfilter(const xzamd_unf_args *a, uint32_t total_tiles, uint32_t kinds, void *stream);
+
 int xzk_malloc(void **p, uint64_t bytes);
 int xzk_free(void *p);
 int xzk_host_alloc(void **p, uint64_t bytes);

@@ -382,6 +382,482 @@ __global__ __launch_bounds__(256) void k_dec_compare(const uint8_t* __restrict__
     if (bad) atomicAdd(mismatches, (unsigned long long)bad);
 }
 
+// ------------------------------------------------------------------------------------------
+// Inverse filters: what the reference's decoder chain runs behind the LZMA2 decoder of a Block
+// (simple/simple_coder.c with the decoder branch of x86.c, powerpc.c, ia64.c, arm.c, armthumb.c, sparc.c,
+// arm64.c, riscv.c:633-753; delta/delta_decoder.c), one fresh filter per Block, start offset 0.
+// A stage reads one buffer and writes another (xzamd_unf_args), because the chunk owners of the x86 and
+// RISC-V walks read bytes a neighbouring owner is about to patch.  Work is cut into tiles of
+// XZAMD_UNF_TILE bytes of a Block; tile_first maps a tile to its Block, so Blocks may differ in length
+// and in chain.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t UNF_TILE = XZAMD_UNF_TILE;
+constexpr uint32_t UNF_ROW = XZAMD_UNF_ROW;
+constexpr uint32_t UNF_CHUNK = UNF_TILE / 256;       // bytes per owner thread of the x86 / RISC-V walks
+
+struct UnfTile {
+    const uint8_t* src;     // the Block's bytes before this stage
+    uint8_t* dst;           // ... and after it
+    uint32_t usize;         // the Block's length
+    uint32_t t;             // tile inside the Block
+    uint32_t ntiles;
+    uint32_t filt;          // id | parameter << 8; 0 = copy
+    uint32_t block;
+};
+
+// wave-uniform: which Block a tile of the stage belongs to
+__device__ __forceinline__ void unf_locate(const xzamd_unf_args& a, uint32_t tile, UnfTile& T)
+{
+    uint32_t lo = 0, hi = a.nblocks;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.tile_first[mid] <= tile) lo = mid; else hi = mid; }
+    const xzamd_dec_chain& ch = a.chains[lo];
+    const uint64_t upos = a.blocks[lo].upos;
+    T.block = lo;
+    T.usize = (uint32_t)a.blocks[lo].usize;
+    T.t = tile - a.tile_first[lo];
+    T.ntiles = a.tile_first[lo + 1] - a.tile_first[lo];
+    T.filt = ch.n > a.stage ? ch.f[ch.n - 1 - a.stage] : 0u;
+    T.src = ((a.stage & 1) ? a.t1 : a.t0) + upos;
+    T.dst = (a.stage + 1 >= ch.n ? a.out : ((a.stage & 1) ? a.t0 : a.t1)) + upos;
+}
+
+// 16 bytes from / to any address; `valid` < 16: only that many bytes exist (the rest read as zero)
+__device__ __forceinline__ uint4 ld16(const uint8_t* p, uint32_t valid)
+{
+    uint4 v;
+    if (valid >= 16) {
+        if (((uintptr_t)p & 15) == 0) return *reinterpret_cast<const uint4*>(p);
+        __builtin_memcpy(&v, p, 16);
+        return v;
+    }
+    uint32_t w[4] = { 0, 0, 0, 0 };
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i)
+        if (i < valid) w[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+    v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    return v;
+}
+__device__ __forceinline__ void st16(uint8_t* p, uint4 v, uint32_t valid)
+{
+    if (valid >= 16) {
+        if (((uintptr_t)p & 15) == 0) *reinterpret_cast<uint4*>(p) = v;
+        else __builtin_memcpy(p, &v, 16);
+        return;
+    }
+    const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i)
+        if (i < valid) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+}
+
+// dst = src for every tile of the stage that is not delta (the BCJ kernels below write converted operands only)
+__global__ __launch_bounds__(256) void k_unf_copy(xzamd_unf_args a)
+{
+    UnfTile T;
+    unf_locate(a, blockIdx.x, T);
+    if ((T.filt & 0xFFu) == 3u) return;
+    const uint32_t base = T.t * UNF_TILE;
+#pragma unroll
+    for (uint32_t i = 0; i < UNF_TILE / 4096; ++i) {
+        const uint32_t p = base + i * 4096 + threadIdx.x * 16;
+        if (p >= T.usize) break;
+        const uint32_t valid = min(16u, T.usize - p);
+        st16(T.dst + p, ld16(T.src + p, valid), valid);
+    }
+}
+
+__device__ __forceinline__ bool x86_is_op(uint32_t b) { return (b & 0xFEu) == 0xE8u; }
+__device__ __forceinline__ bool x86_ms(uint32_t b) { return b == 0u || b == 0xFFu; }
+
+// x86 (simple/x86.c:26-118, is_encoder = false).  The argument above k_x86_bcj (lzma_kernels.hip) holds for this
+// direction word for word: every decision of the decoder reads its own INPUT only (the filtered bytes: a converted
+// operand is skipped, never read again), and (prev_mask, prev_pos) are void at a position with five bytes without
+// E8 / E9 in front of it.  So the owner of chunk k starts at the first such synchronisation point of its chunk and
+// runs to the first one at or behind the chunk end; without synchronisation points one thread walks on: serial, exact.
+__device__ void unf_x86(const uint8_t* __restrict__ b, uint8_t* __restrict__ o, uint32_t size, uint32_t k)
+{
+    if (size < 5) return;
+    const uint32_t limit = size - 5;                 // last position the filter examines
+    const uint32_t s = k * UNF_CHUNK;
+    if (s > limit) return;
+    const uint32_t e = s + UNF_CHUNK;
+    uint32_t pos = 0, run = 0;                       // run = non-opcode bytes immediately before pos
+    if (k != 0) {
+        bool found = false;
+        for (uint32_t q = s - 5; q <= limit && q < e; ++q) {
+            if (q >= s && run >= 5) { pos = q; found = true; break; }
+            run = x86_is_op(b[q]) ? 0u : run + 1;
+        }
+        if (!found) return;                           // the previous owner runs through this chunk
+    }
+    uint32_t prev_mask = 0, prev_pos = pos - 6;       // "long ago"
+    while (pos <= limit) {
+        if (pos >= e && run >= 5) break;              // the next owner's start
+        const uint32_t c = b[pos];
+        if (!x86_is_op(c)) { ++pos; ++run; continue; }
+        const uint32_t offset = pos - prev_pos;
+        prev_pos = pos;
+        if (offset > 5) prev_mask = 0;
+        else for (uint32_t i = 0; i < offset; ++i) prev_mask = (prev_mask & 0x77u) << 1;
+        const uint32_t b4 = b[pos + 4];
+        if (x86_ms(b4) && (prev_mask >> 1) <= 4 && (prev_mask >> 1) != 3) {
+            const uint32_t b1 = b[pos + 1], b2 = b[pos + 2], b3 = b[pos + 3];
+            uint32_t src = (b4 << 24) | (b3 << 16) | (b2 << 8) | b1;
+            uint32_t dest;
+            for (;;) {
+                dest = src - (pos + 5);
+                if (prev_mask == 0) break;
+                const uint32_t pm = prev_mask >> 1;
+                const uint32_t i = pm == 0 ? 0u : pm == 1 ? 1u : pm <= 3 ? 2u : 3u;
+                const uint32_t bb = (dest >> (24 - i * 8)) & 0xFFu;
+                if (!x86_ms(bb)) break;
+                src = dest ^ ((1u << (32 - i * 8)) - 1);
+            }
+            o[pos + 4] = (uint8_t)(~(((dest >> 24) & 1) - 1));
+            o[pos + 3] = (uint8_t)(dest >> 16);
+            o[pos + 2] = (uint8_t)(dest >> 8);
+            o[pos + 1] = (uint8_t)dest;
+            run = x86_is_op(b1) ? 0u : 1u;
+            run = x86_is_op(b2) ? 0u : run + 1;
+            run = x86_is_op(b3) ? 0u : run + 1;
+            run = x86_is_op(b4) ? 0u : run + 1;
+            pos += 5;
+            prev_mask = 0;
+        } else {
+            ++pos;
+            run = 0;
+            prev_mask |= 1;
+            if (x86_ms(b4)) prev_mask |= 0x10;
+        }
+    }
+}
+
+// RISC-V (simple/riscv.c:633-753, decoder).  The decoder examines a position with the same tests as the encoder
+// (a JAL with rd x1 / x5; an AUIPC whose rd is not x0 / x2 and that pairs with the next instruction: the "fake" pair it
+// re-encodes; an AUIPC in the special form: the real pair it restores) and jumps 2, 4, 6 or 8 bytes accordingly, reading
+// only bytes no earlier conversion wrote.  So the walk is cut into chunks by the rule of k_riscv_bcj: a position that
+// none of its three predecessors can jump over is examined by every walk.
+__device__ __forceinline__ uint32_t rv_rd32(const uint8_t* p)
+{
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+__device__ __forceinline__ void rv_wr32(uint8_t* p, uint32_t v)
+{
+    p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
+}
+__device__ __forceinline__ bool rv_not_pair(uint32_t auipc, uint32_t inst2) { return (((auipc << 8) ^ inst2) & 0xF8003u) != 3u; }
+__device__ __forceinline__ bool rv_special(uint32_t auipc) { return (auipc & 0x3FFFu) == 0x3117u && ((auipc >> 27) & 0x1Du) != 0; }
+__device__ __forceinline__ uint32_t rv_step(const uint8_t* b, uint32_t i, uint32_t limit)
+{
+    if (i > limit) return 2;
+    const uint32_t b0 = b[i];
+    if (b0 == 0xEFu) return (b[i + 1] & 0x0Du) ? 2u : 4u;
+    if ((b0 & 0x7Fu) != 0x17u) return 2;
+    const uint32_t inst = rv_rd32(b + i);
+    if (inst & 0xE80u) return rv_not_pair(inst, rv_rd32(b + i + 4)) ? 6u : 8u;
+    return rv_special(inst) ? 8u : 4u;
+}
+__device__ __forceinline__ bool rv_sync(const uint8_t* b, uint32_t i, uint32_t limit)
+{
+    return (i < 2 || rv_step(b, i - 2, limit) <= 2) && (i < 4 || rv_step(b, i - 4, limit) <= 4) && (i < 6 || rv_step(b, i - 6, limit) <= 6);
+}
+
+__device__ void unf_riscv(const uint8_t* __restrict__ b, uint8_t* __restrict__ o, uint32_t size, uint32_t k)
+{
+    if (size < 8) return;
+    const uint32_t limit = size - 8;                 // last position the filter examines
+    const uint32_t s = k * UNF_CHUNK;                // even
+    if (s > limit) return;
+    const uint32_t e = s + UNF_CHUNK;
+    uint32_t pos = 0;
+    if (k != 0) {
+        bool found = false;
+        for (uint32_t q = s; q <= limit && q < e; q += 2)
+            if (rv_sync(b, q, limit)) { pos = q; found = true; break; }
+        if (!found) return;                          // the previous owner walks through this chunk
+    }
+    while (pos <= limit) {
+        if (pos >= e && rv_sync(b, pos, limit)) break;      // the next owner's start
+        const uint32_t b0 = b[pos];
+        if (b0 == 0xEFu) {
+            // JAL: absolute address, big endian -> the pc-relative immediate in its four pieces
+            const uint32_t b1 = b[pos + 1];
+            if (b1 & 0x0Du) { pos += 2; continue; }
+            const uint32_t b2 = b[pos + 2], b3 = b[pos + 3];
+            uint32_t addr = ((b1 & 0xF0u) << 13) | (b2 << 9) | (b3 << 1);
+            addr -= pos;
+            o[pos + 1] = (uint8_t)((b1 & 0x0Fu) | ((addr >> 8) & 0xF0u));
+            o[pos + 2] = (uint8_t)(((addr >> 16) & 0x0Fu) | ((addr >> 7) & 0x10u) | ((addr << 4) & 0xE0u));
+            o[pos + 3] = (uint8_t)(((addr >> 4) & 0x7Fu) | ((addr >> 13) & 0x80u));
+            pos += 4;
+        } else if ((b0 & 0x7Fu) == 0x17u) {
+            uint32_t inst = rv_rd32(b + pos), inst2;
+            if (inst & 0xE80u) {
+                // rd other than x0 / x2: a "fake" pair goes back into the special form (no sign extension, no pc)
+                inst2 = rv_rd32(b + pos + 4);
+                if (rv_not_pair(inst, inst2)) { pos += 6; continue; }
+                const uint32_t addr = (inst & 0xFFFFF000u) + (inst2 >> 20);
+                inst = 0x17u | (2u << 7) | (inst2 << 12);
+                inst2 = addr;
+            } else {
+                // rd x0 / x2: the special form the encoder wrote becomes the real AUIPC pair again
+                if (!rv_special(inst)) { pos += 4; continue; }
+                const uint32_t rs1 = inst >> 27;
+                const uint8_t* q = b + pos + 4;
+                uint32_t addr = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+                addr -= pos;
+                inst2 = (inst >> 12) | (addr << 20);
+                inst = 0x17u | (rs1 << 7) | ((addr + 0x800u) & 0xFFFFF000u);
+            }
+            rv_wr32(o + pos, inst);
+            rv_wr32(o + pos + 4, inst2);
+            pos += 8;
+        } else {
+            pos += 2;
+        }
+    }
+}
+
+// PowerPC / IA-64 / ARM / ARM-Thumb / SPARC / ARM64: one aligned slot = one thread's work item, pc = offset in the
+// Block, subtraction where the encoder adds; the tail shorter than a slot stays as it is.  An ARM-Thumb BL pair keeps
+// its 0xF0 / 0xF8 marker bits when it is converted, so here too the halfword behind a pair cannot start another one
+// and the slots are independent.
+__device__ void unf_slot(const uint8_t* __restrict__ b, uint8_t* __restrict__ o, uint32_t blen, uint32_t pc, uint32_t kind)
+{
+    const uint8_t* p = b + pc;
+    uint8_t* q = o + pc;
+    if (kind == 8) {                                      // ARM-Thumb BL pair
+        if (blen < 4 || pc > blen - 4) return;
+        if ((p[1] & 0xF8u) != 0xF0u || (p[3] & 0xF8u) != 0xF8u) return;
+        uint32_t src = ((uint32_t)(p[1] & 7u) << 19) | ((uint32_t)p[0] << 11) | ((uint32_t)(p[3] & 7u) << 8) | p[2];
+        src <<= 1;
+        const uint32_t dest = (src - (pc + 4)) >> 1;
+        q[1] = (uint8_t)(0xF0u | ((dest >> 19) & 7u));
+        q[0] = (uint8_t)(dest >> 11);
+        q[3] = (uint8_t)(0xF8u | ((dest >> 8) & 7u));
+        q[2] = (uint8_t)dest;
+    } else if (kind == 6) {                               // IA-64 bundle
+        if (pc + 16 > (blen & ~15u)) return;
+        uint8_t bun[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) bun[i] = p[i];
+        const uint32_t tmpl = bun[0] & 0x1Fu;
+        // branch slots by template: 16,17: 4  18,19: 6  22,23: 7  24,25,28,29: 4
+        const uint32_t mask = (tmpl == 16 || tmpl == 17 || tmpl == 24 || tmpl == 25 || tmpl == 28 || tmpl == 29) ? 4u
+                : (tmpl == 18 || tmpl == 19) ? 6u : (tmpl == 22 || tmpl == 23) ? 7u : 0u;
+        bool changed = false;
+        uint32_t bit_pos = 5;
+        for (uint32_t slot = 0; slot < 3; ++slot, bit_pos += 41) {
+            if (((mask >> slot) & 1u) == 0) continue;
+            const uint32_t byte_pos = bit_pos >> 3, bit_res = bit_pos & 7u;
+            uint64_t instruction = 0;
+            for (uint32_t j = 0; j < 6; ++j) instruction += (uint64_t)bun[j + byte_pos] << (8 * j);
+            uint64_t norm = instruction >> bit_res;
+            if (((norm >> 37) & 0xFu) != 0x5u || ((norm >> 9) & 0x7u) != 0) continue;
+            uint32_t src = (uint32_t)((norm >> 13) & 0xFFFFFu);
+            src |= (uint32_t)((norm >> 36) & 1u) << 20;
+            src <<= 4;
+            const uint32_t dest = (src - pc) >> 4;
+            norm &= ~((uint64_t)0x8FFFFF << 13);
+            norm |= (uint64_t)(dest & 0xFFFFFu) << 13;
+            norm |= (uint64_t)(dest & 0x100000u) << (36 - 20);
+            instruction &= (1u << bit_res) - 1;
+            instruction |= norm << bit_res;
+            for (uint32_t j = 0; j < 6; ++j) bun[j + byte_pos] = (uint8_t)(instruction >> (8 * j));
+            changed = true;
+        }
+        if (changed) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) q[i] = bun[i];
+        }
+    } else {
+        if (pc + 4 > (blen & ~3u)) return;
+        if (kind == 0x0A) {                               // ARM64 BL / ADRP (little endian)
+            uint32_t instr = rv_rd32(p);
+            if ((instr >> 26) == 0x25) {
+                instr = 0x94000000u | ((instr - (pc >> 2)) & 0x03FFFFFFu);
+                rv_wr32(q, instr);
+            } else if ((instr & 0x9F000000u) == 0x90000000u) {
+                const uint32_t src = ((instr >> 29) & 3) | ((instr >> 3) & 0x001FFFFCu);
+                if ((src + 0x00020000u) & 0x001C0000u) return;      // outside +/-512 MiB: not converted, in either direction
+                instr &= 0x9000001Fu;
+                const uint32_t dest = src - (pc >> 12);
+                instr |= (dest & 3) << 29;
+                instr |= (dest & 0x0003FFFCu) << 3;
+                instr |= (0u - (dest & 0x00020000u)) & 0x00E00000u;
+                rv_wr32(q, instr);
+            }
+        } else if (kind == 7) {                           // ARM BL (little endian, condition "always")
+            if (p[3] != 0xEBu) return;
+            uint32_t src = ((uint32_t)p[2] << 16) | ((uint32_t)p[1] << 8) | p[0];
+            src <<= 2;
+            const uint32_t dest = (src - (pc + 8)) >> 2;
+            q[2] = (uint8_t)(dest >> 16); q[1] = (uint8_t)(dest >> 8); q[0] = (uint8_t)dest;
+        } else if (kind == 5) {                           // PowerPC b/bl with AA = 0, LK = 1 (big endian)
+            if ((p[0] >> 2) != 0x12u || (p[3] & 3u) != 1u) return;
+            const uint32_t src = ((uint32_t)(p[0] & 3u) << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (p[3] & ~3u);
+            const uint32_t dest = src - pc;
+            q[0] = (uint8_t)(0x48u | ((dest >> 24) & 3u));
+            q[1] = (uint8_t)(dest >> 16);
+            q[2] = (uint8_t)(dest >> 8);
+            q[3] = (uint8_t)((p[3] & 3u) | (dest & 0xFFu));
+        } else if (kind == 9) {                           // SPARC call (big endian)
+            if (!((p[0] == 0x40u && (p[1] & 0xC0u) == 0x00u) || (p[0] == 0x7Fu && (p[1] & 0xC0u) == 0xC0u))) return;
+            uint32_t src = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+            src <<= 2;
+            uint32_t dest = (src - pc) >> 2;
+            dest = (((0u - ((dest >> 22) & 1u)) << 22) & 0x3FFFFFFFu) | (dest & 0x3FFFFFu) | 0x40000000u;
+            q[0] = (uint8_t)(dest >> 24); q[1] = (uint8_t)(dest >> 16); q[2] = (uint8_t)(dest >> 8); q[3] = (uint8_t)dest;
+        }
+    }
+}
+
+// one workgroup per tile: the Block's BCJ filter of this stage (k_unf_copy has made dst a copy of src)
+__global__ __launch_bounds__(256) void k_unf_bcj(xzamd_unf_args a)
+{
+    UnfTile T;
+    unf_locate(a, blockIdx.x, T);
+    const uint32_t kind = T.filt & 0xFFu;
+    if (kind < 4u || kind > 0x0Bu) return;                // copy or delta
+    if (kind == 4u) unf_x86(T.src, T.dst, T.usize, T.t * 256 + threadIdx.x);
+    else if (kind == 0x0Bu) unf_riscv(T.src, T.dst, T.usize, T.t * 256 + threadIdx.x);
+    else {
+        const uint32_t unit = kind == 8u ? 2u : kind == 6u ? 16u : 4u;
+        const uint32_t base = T.t * UNF_TILE;
+        for (uint32_t s = threadIdx.x; s < UNF_TILE / unit; s += 256) {
+            const uint32_t pc = base + s * unit;
+            if (pc >= T.usize) break;
+            unf_slot(T.src, T.dst, T.usize, pc, kind);
+        }
+    }
+}
+
+// ---- delta (delta/delta_decoder.c): out[i] = in[i] + out[i - dist] inside a Block, zero history -----------------
+// = dist interleaved prefix sums of bytes (mod 256), as a three-step segmented scan over tiles of UNF_TILE bytes:
+//   k_delta_tile_sums   per tile, the byte sum of every residue class i mod dist;
+//   k_delta_block_scan  per Block, the exclusive scan of the tile vectors (one lane per residue class);
+//   k_delta_apply       per tile, the local scan with its carry-in, written out.
+// A wavefront holds 1024 consecutive bytes, 16 per lane (one dwordx4), and scans them by doubling: v += v shifted up
+// by dist, 2 dist, 4 dist ... bytes, each shift a lane shift (ds_bpermute) plus a byte alignment, the adds packed
+// 4 x u8 without carries between bytes.  It walks its tile in 16 such pieces; the carry from piece to piece (and
+// from tile to tile) is "the dist output bytes in front of the piece", added to the piece's first dist input bytes --
+// which is the recurrence itself, so no per-class bookkeeping is needed inside a tile.
+__device__ __forceinline__ uint32_t padd8(uint32_t a, uint32_t b)
+{
+    return ((a & 0x7F7F7F7Fu) + (b & 0x7F7F7F7Fu)) ^ ((a ^ b) & 0x80808080u);
+}
+__device__ __forceinline__ uint4 padd8(uint4 a, uint4 b)
+{
+    return make_uint4(padd8(a.x, b.x), padd8(a.y, b.y), padd8(a.z, b.z), padd8(a.w, b.w));
+}
+__device__ __forceinline__ uint4 lane_get(uint4 v, int lane, int src)
+{
+    const bool ok = src >= 0 && src < 64;
+    const int addr = (ok ? src : lane) << 2;
+    uint4 r;
+    r.x = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v.x);
+    r.y = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v.y);
+    r.z = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v.z);
+    r.w = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v.w);
+    return ok ? r : make_uint4(0, 0, 0, 0);
+}
+// The 16 bytes at byte offset 16 * lane + off of the wavefront's 1024-byte vector (zeros outside it); off is wave-uniform.
+__device__ __forceinline__ uint4 wave_bytes_at(uint4 v, int off)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    const int fq = off >> 4;                              // floor
+    const uint32_t r = (uint32_t)off & 15u;
+    const uint4 A = lane_get(v, lane, lane + fq);
+    if (r == 0) return A;
+    const uint4 B = lane_get(v, lane, lane + fq + 1);
+    const uint32_t rb = r & 3u;
+#define XZ_AB(hi, lo) __builtin_amdgcn_alignbyte((hi), (lo), rb)
+    switch (r >> 2) {
+    case 0: return make_uint4(XZ_AB(A.y, A.x), XZ_AB(A.z, A.y), XZ_AB(A.w, A.z), XZ_AB(B.x, A.w));
+    case 1: return make_uint4(XZ_AB(A.z, A.y), XZ_AB(A.w, A.z), XZ_AB(B.x, A.w), XZ_AB(B.y, B.x));
+    case 2: return make_uint4(XZ_AB(A.w, A.z), XZ_AB(B.x, A.w), XZ_AB(B.y, B.x), XZ_AB(B.z, B.y));
+    default: return make_uint4(XZ_AB(B.x, A.w), XZ_AB(B.y, B.x), XZ_AB(B.z, B.y), XZ_AB(B.w, B.z));
+    }
+#undef XZ_AB
+}
+
+// Scan one tile (bytes [t0, t0 + UNF_TILE) of a Block of `usize` bytes; bytes behind the Block count as zeros).
+// `tail` = vector whose first dist bytes are the dist output bytes in front of the tile; returns the same for the
+// position behind the tile.
+template <bool WRITE>
+__device__ __forceinline__ uint4 delta_tile(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint32_t usize,
+        uint32_t t0, uint32_t dist, uint4 tail)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t c = 0; c < UNF_TILE; c += 1024) {
+        if (WRITE && t0 + c >= usize) break;
+        const uint32_t p = t0 + c + lane * 16;
+        const uint32_t valid = p < usize ? min(16u, usize - p) : 0u;
+        uint4 v = padd8(ld16(src + p, valid), tail);
+        for (uint32_t k = dist; k < 1024; k <<= 1) v = padd8(v, wave_bytes_at(v, -(int)k));
+        if (WRITE) st16(dst + p, v, valid);
+        tail = wave_bytes_at(v, 1024 - (int)dist);
+    }
+    return tail;
+}
+
+__global__ __launch_bounds__(64) void k_delta_tile_sums(xzamd_unf_args a)
+{
+    UnfTile T;
+    unf_locate(a, blockIdx.x, T);
+    if ((T.filt & 0xFFu) != 3u || T.t + 1 >= T.ntiles) return;     // nobody reads the sums of a Block's last tile
+    const uint32_t dist = (T.filt >> 8) + 1;
+    const uint4 tail = delta_tile<false>(T.src, nullptr, T.usize, T.t * UNF_TILE, dist, make_uint4(0, 0, 0, 0));
+    // byte j of the row = sum of the residue class of Block offset (tile end + j), j < dist; zeros behind
+    if (threadIdx.x < UNF_ROW / 16)
+        *reinterpret_cast<uint4*>(a.tile_sum + (uint64_t)blockIdx.x * UNF_ROW + threadIdx.x * 16) = tail;
+}
+
+// One workgroup per Block, lane r = residue class r: carry row of tile t, byte j = the output byte at Block offset
+// (tile start - dist + j) = the sum of class (tile start + j) mod dist over the tiles in front.
+__global__ __launch_bounds__(256) void k_delta_block_scan(xzamd_unf_args a)
+{
+    const uint32_t b = blockIdx.x;
+    const xzamd_dec_chain& ch = a.chains[b];
+    const uint32_t filt = ch.n > a.stage ? ch.f[ch.n - 1 - a.stage] : 0u;
+    if ((filt & 0xFFu) != 3u) return;
+    const uint32_t first = a.tile_first[b], ntiles = a.tile_first[b + 1] - first;
+    const uint32_t dist = (filt >> 8) + 1, step = UNF_TILE % dist;
+    const uint32_t r = threadIdx.x;
+    const bool active = r < dist;
+    const uint8_t* __restrict__ S = a.tile_sum + (uint64_t)first * UNF_ROW;
+    uint8_t* __restrict__ C = a.tile_carry + (uint64_t)first * UNF_ROW;
+    uint32_t acc = 0, jc = active ? r : 0u;               // jc: class r's byte in the carry row of tile t
+    for (uint32_t t = 0; t < ntiles; t += 8) {
+        uint32_t j[9], s[8];
+        j[0] = jc;
+#pragma unroll
+        for (uint32_t u = 0; u < 8; ++u) {
+            j[u + 1] = j[u] >= step ? j[u] - step : j[u] + dist - step;     // ... = its byte in the sum row of tile t
+            s[u] = (active && t + u + 1 < ntiles) ? S[(uint64_t)(t + u) * UNF_ROW + j[u + 1]] : 0u;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 8; ++u) {
+            if (t + u >= ntiles) break;
+            C[(uint64_t)(t + u) * UNF_ROW + (active ? j[u] : r)] = active ? (uint8_t)acc : (uint8_t)0;
+            acc += s[u];
+        }
+        jc = j[8];
+    }
+}
+
+__global__ __launch_bounds__(64) void k_delta_apply(xzamd_unf_args a)
+{
+    UnfTile T;
+    unf_locate(a, blockIdx.x, T);
+    if ((T.filt & 0xFFu) != 3u) return;
+    const uint32_t dist = (T.filt >> 8) + 1;
+    uint4 tail = make_uint4(0, 0, 0, 0);
+    if (threadIdx.x < UNF_ROW / 16)
+        tail = *reinterpret_cast<const uint4*>(a.tile_carry + (uint64_t)blockIdx.x * UNF_ROW + threadIdx.x * 16);
+    delta_tile<true>(T.src, T.dst, T.usize, T.t * UNF_TILE, dist, tail);
+}
+
 } // namespace
 
 extern "C" {
@@ -414,6 +890,20 @@ int xzk_dec_compare(const uint8_t* a, const uint8_t* b, uint64_t n, unsigned lon
     if (g > 65536) g = 65536;
     if (g == 0) g = 1;
     hipLaunchKernelGGL(k_dec_compare, dim3((uint32_t)g), dim3(256), 0, (hipStream_t)stream_, a, b, n, d_mismatches);
+    return (int)hipGetLastError();
+}
+
+int xzk_dec_unfilter(const xzamd_unf_args* a, uint32_t total_tiles, uint32_t kinds, void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    if (total_tiles == 0 || a->nblocks == 0) return 0;
+    if (kinds & XZAMD_UNF_COPY) hipLaunchKernelGGL(k_unf_copy, dim3(total_tiles), dim3(256), 0, st, *a);
+    if (kinds & XZAMD_UNF_BCJ) hipLaunchKernelGGL(k_unf_bcj, dim3(total_tiles), dim3(256), 0, st, *a);
+    if (kinds & XZAMD_UNF_DELTA) {
+        hipLaunchKernelGGL(k_delta_tile_sums, dim3(total_tiles), dim3(64), 0, st, *a);
+        hipLaunchKernelGGL(k_delta_block_scan, dim3(a->nblocks), dim3(256), 0, st, *a);
+        hipLaunchKernelGGL(k_delta_apply, dim3(total_tiles), dim3(64), 0, st, *a);
+    }
     return (int)hipGetLastError();
 }
 

@@ -8,11 +8,27 @@
  *                                           sizes must match the Blocks)
  *   common/block_header_decoder.c:17-125    Block Header (size, flags, VLIs, filter flags, padding, CRC32)
  *   common/block_decoder.c:47-230           Compressed / Uncompressed Size vs the header, Block Padding, Check
+ *   common/filter_flags_decoder.c:15-45,    Filter Flags: ids, sizes of properties, the rules of a chain (1 to 4 filters,
+ *   filter_common.c:250-294,                LZMA2 last and only last), BCJ properties (none, or a 4-byte start offset),
+ *   simple/simple_decoder.c:15-39,          delta properties (one byte, distance - 1)
+ *   delta/delta_decoder.c:67-85
  *   lzma/lzma2_decoder.c, lzma_decoder.c    -> k_dec_scan / k_dec_units
+ *   simple/ (the decoder direction),       -> xzk_dec_unfilter: the inverse filters, last filter of the chain first
+ *   delta/delta_decoder.c:17-25
  *   check/crc32_fast.c, crc64_fast.c        -> the encoder's k_crc_strips / k_crc_fold over the decoded bytes
  * Scheduling model of common/stream_decoder_mt.c: independent Blocks in parallel; with the original data at
  * hand (verification) every state-resetting chunk chain is its own unit.
- * Supported: one Stream, filter chain {LZMA2}, checks none / CRC32 / CRC64 (SHA-256 is skipped, not verified).
+ * Supported: one Stream; the filter chains {LZMA2} and {up to three of: delta | x86 | PowerPC | IA-64 | ARM | ARM-Thumb |
+ * SPARC | ARM64 | RISC-V, LZMA2}, which may differ from Block to Block; checks none / CRC32 / CRC64 / SHA-256, all
+ * verified.  Declined with XZAMD_OPTIONS_ERROR: a BCJ filter with a non-zero start offset (nothing in this project
+ * writes one), every other filter id, every chain the reference's lzma_validate_chain refuses.
+ *
+ * Buffers of a Stream with filtered Blocks: the LZMA2 stage decodes into a temporary, each inverse stage reads one
+ * buffer and writes another (a second temporary for chains of two or three filters), the last stage of a Block writes
+ * d_out.  A Stream whose Blocks are all {LZMA2} allocates no temporary and launches no inverse stage.
+ * Verification decode of a filtered Stream: the history of the span-parallel units is the FILTERED original, made with
+ * the encoder's own forward kernels when the Blocks form the geometry our encoder writes (equally long but the last,
+ * one chain); otherwise unit = Block.  The decoded, unfiltered bytes are compared with the original either way.
  */
 #include "xzamd_internal.h"
 #include "kernels_api.h"
@@ -21,6 +37,15 @@
 #include <string.h>
 
 #define FORMAT_ERROR 7      /* LZMA_FORMAT_ERROR */
+
+/* test instrumentation (not public API): [0] temporary buffers allocated for inverse filters, [1] xzk_dec_unfilter calls,
+ * [2] forward-filter launches of verification decodes; process-wide, since the library was loaded */
+static uint64_t dec_counters[3];
+void xzamd_debug_decode_counters_(uint64_t out[3])
+{
+	for (int i = 0; i < 3; ++i) out[i] = __atomic_load_n(&dec_counters[i], __ATOMIC_RELAXED);
+}
+static void count_(int i) { __atomic_fetch_add(&dec_counters[i], 1, __ATOMIC_RELAXED); }
 
 static int vli_get(const uint8_t *p, size_t n, size_t *pos, uint64_t *v)
 {
@@ -62,6 +87,11 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 	void *d_sha = NULL;
 	uint32_t *unit_first = NULL, *h_err = NULL;
 	void *d_blocks = NULL, *d_units = NULL, *d_first = NULL, *d_lit = NULL, *d_misc = NULL, *d_strip = NULL, *d_crc = NULL;
+	xzamd_dec_chain *hc = NULL;        /* per Block: the filters in front of LZMA2 */
+	uint32_t *tile_first = NULL;
+	void *d_chains = NULL, *d_tiles = NULL, *d_t0 = NULL, *d_t1 = NULL, *d_filt = NULL, *d_tsum = NULL, *d_tcarry = NULL;
+	uint32_t max_nf = 0;
+	int any_filtered = 0, any_plain = 0;
 	*out_size = 0;
 	if (mismatches) *mismatches = 0;
 	if (nblocks_out) *nblocks_out = 0;
@@ -107,7 +137,9 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 	stored32 = (uint8_t *)calloc(nb ? nb : 1, 32);
 	if (!stored32) FAILD(XZAMD_MEM_ERROR, "malloc");
 	unit_first = (uint32_t *)calloc(nb + 1, 4);
-	if (!hb || !stored || !h_crc || !h_err || !unit_first) FAILD(XZAMD_MEM_ERROR, "malloc");
+	hc = (xzamd_dec_chain *)calloc(nb ? nb : 1, sizeof(*hc));
+	tile_first = (uint32_t *)calloc(nb + 1, 4);
+	if (!hb || !stored || !h_crc || !h_err || !unit_first || !hc || !tile_first) FAILD(XZAMD_MEM_ERROR, "malloc");
 	uint64_t pos = 12, utotal = 0, max_usize = 0;
 	for (uint64_t b = 0; b < nb; ++b) {
 		uint64_t unpadded = 0, usize = 0;
@@ -131,21 +163,45 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 			FAILD(XZAMD_DATA_ERROR, "Block Header CRC32");
 		if (bh[1] & 0x3C)
 			FAILD(XZAMD_OPTIONS_ERROR, "reserved Block Flags");
-		if ((bh[1] & 3) != 0)
-			FAILD(XZAMD_OPTIONS_ERROR, "only the {LZMA2} filter chain is decoded on the device");
 		size_t hp = 2;
-		uint64_t h_csize = UINT64_MAX, h_usize = UINT64_MAX, fid = 0, fps = 0;
+		uint64_t h_csize = UINT64_MAX, h_usize = UINT64_MAX;
 		if ((bh[1] & 0x40) && vli_get(bh, hs - 4, &hp, &h_csize)) FAILD(XZAMD_DATA_ERROR, "Block Header Compressed Size");
 		if ((bh[1] & 0x80) && vli_get(bh, hs - 4, &hp, &h_usize)) FAILD(XZAMD_DATA_ERROR, "Block Header Uncompressed Size");
-		if (vli_get(bh, hs - 4, &hp, &fid) || vli_get(bh, hs - 4, &hp, &fps))
-			FAILD(XZAMD_DATA_ERROR, "Filter Flags");
-		if (fid != 0x21 || fps != 1 || hp >= hs - 4)
-			FAILD(XZAMD_OPTIONS_ERROR, "only the {LZMA2} filter chain is decoded on the device");
-		const uint32_t db = bh[hp++];
-		if (db > 40) FAILD(XZAMD_OPTIONS_ERROR, "LZMA2 dictionary size byte");
+		/* Filter Flags, one after another as the reference reads them: the first error decides the code */
+		const uint32_t nfilt = (bh[1] & 3u) + 1;
+		uint32_t db = 0, lzma2_at = UINT32_MAX, nlzma2 = 0;
+		for (uint32_t i = 0; i < nfilt; ++i) {
+			uint64_t fid = 0, fps = 0;
+			if (vli_get(bh, hs - 4, &hp, &fid) || fid >= (1ull << 62) || vli_get(bh, hs - 4, &hp, &fps) || hs - 4 - hp < fps)
+				FAILD(XZAMD_DATA_ERROR, "Filter Flags");
+			const uint8_t *props = bh + hp;
+			uint32_t entry = 0;
+			if (fid == 0x21) {
+				if (fps != 1 || props[0] > 40) FAILD(XZAMD_OPTIONS_ERROR, "LZMA2 properties (dictionary size byte)");
+				db = props[0];
+				lzma2_at = i;
+				++nlzma2;
+			} else if (fid == 0x03) {
+				if (fps != 1) FAILD(XZAMD_OPTIONS_ERROR, "delta filter: size of properties");
+				entry = 3u | ((uint32_t)props[0] << 8);
+			} else if (fid >= 0x04 && fid <= 0x0B) {
+				if (fps != 0 && fps != 4) FAILD(XZAMD_OPTIONS_ERROR, "BCJ filter: size of properties");
+				if (fps == 4 && rd32(props) != 0)
+					FAILD(XZAMD_OPTIONS_ERROR, "BCJ filter with a non-zero start offset is not decoded on the device");
+				entry = (uint32_t)fid;
+			} else {
+				FAILD(XZAMD_OPTIONS_ERROR, "filter id the device decoder does not know");
+			}
+			if (entry && hc[b].n < XZAMD_DEC_FILTERS_MAX) hc[b].f[hc[b].n++] = entry;
+			hp += fps;
+		}
+		for (size_t q = hp; q < hs - 4; ++q)
+			if (bh[q] != 0) FAILD(XZAMD_OPTIONS_ERROR, "Block Header padding");
+		/* filter_common.c:250-294: LZMA2 ends the chain and stands nowhere else */
+		if (nlzma2 != 1 || lzma2_at != nfilt - 1)
+			FAILD(XZAMD_OPTIONS_ERROR, "filter chain: LZMA2 must be the last filter and only the last");
+		if (hc[b].n) { any_filtered = 1; if (hc[b].n > max_nf) max_nf = hc[b].n; } else any_plain = 1;
 		const uint32_t dict = db == 40 ? 0xFFFFFFFFu : ((2u | (db & 1u)) << (db / 2 + 11));
-		for (; hp < hs - 4; ++hp)
-			if (bh[hp] != 0) FAILD(XZAMD_OPTIONS_ERROR, "Block Header padding");
 		if (unpadded < hs + csz)
 			FAILD(XZAMD_DATA_ERROR, "Unpadded Size smaller than its header");
 		const uint64_t csize = unpadded - hs - csz;
@@ -198,6 +254,46 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 		uint32_t units_cap = split ? (uint32_t)(max_usize / 4096 + 8) : 1;
 		if ((uint64_t)units_cap * nb > (1ull << 27)) { split = 0; units_cap = 1; }
 		uint32_t waves = xzamd_ctx_wave_slots_(c);
+		uint8_t *dec_out = d_out;          /* where the LZMA2 stage writes */
+		const uint8_t *hist_src = d_expected;
+		if (any_filtered) {
+			/* the LZMA2 stage of every Block decodes into t0 (one kernel, one output base); a second temporary only for
+			 * chains of two or three filters */
+			HIPD(xzk_malloc(&d_t0, utotal + 16), "hipMalloc");
+			count_(0);
+			if (max_nf >= 2) { HIPD(xzk_malloc(&d_t1, utotal + 16), "hipMalloc"); count_(0); }
+			HIPD(xzk_malloc(&d_chains, nb * sizeof(xzamd_dec_chain)), "hipMalloc");
+			HIPD(xzk_malloc(&d_tiles, 4 * (nb + 1)), "hipMalloc");
+			HIPD(xzk_h2d(d_chains, hc, nb * sizeof(xzamd_dec_chain), st), "h2d chains");
+			dec_out = (uint8_t *)d_t0;
+			if (split) {
+				/* The history of a span-parallel unit is what the LZMA2 encoder saw: the filtered original.  Make it with the
+				 * encoder's forward kernels when the Stream has the geometry they filter (Blocks equally long but the last,
+				 * one chain, < 2 GiB); any other Stream: unit = Block. */
+				const uint64_t bs0 = hb[0].usize;
+				int same = !any_plain && bs0 != 0 && utotal < (1ull << 31) && hb[nb - 1].usize <= bs0;
+				for (uint64_t b = 0; same && b < nb; ++b)
+					same = memcmp(&hc[b], &hc[0], sizeof(hc[0])) == 0 && (b + 1 == nb || hb[b].usize == bs0);
+				if (!same) { split = 0; units_cap = 1; }
+				else {
+					HIPD(xzk_malloc(&d_filt, utotal + 16), "hipMalloc");
+					count_(0);
+					const uint32_t nf = hc[0].n;
+					const uint8_t *src = d_expected;
+					for (uint32_t i = 0; i < nf; ++i) {
+						/* in -> F, in -> t0 -> F, in -> F -> t0 -> F: no step in place; t0 is free until the decode */
+						uint8_t *dst = ((nf - 1 - i) & 1) ? (uint8_t *)d_t0 : (uint8_t *)d_filt;
+						const uint32_t f = hc[0].f[i];
+						HIPD(f == 4u ? xzk_x86_bcj(src, dst, (uint32_t)utotal, (uint32_t)bs0, nbk, st)
+								: xzk_prefilter(src, dst, (uint32_t)utotal, (uint32_t)bs0, nbk, f & 0xFFu, (f >> 8) + 1, st),
+								"forward filter of the verification decode");
+						count_(2);
+						src = dst;
+					}
+					hist_src = (const uint8_t *)d_filt;
+				}
+			}
+		}
 		HIPD(xzk_malloc(&d_blocks, nb * sizeof(xzamd_dec_block)), "hipMalloc");
 		HIPD(xzk_malloc(&d_misc, 4096 + 4 * nb), "hipMalloc");
 		HIPD(xzk_malloc(&d_first, 4 * (nb + 1)), "hipMalloc");
@@ -222,7 +318,7 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 			split = 0; units_cap = 1;
 			goto rescan;
 		}
-		const uint8_t *hist = split ? d_expected : NULL;
+		const uint8_t *hist = split ? hist_src : NULL;
 		const uint32_t work = hist ? total_units : nbk;
 		if (waves > work) waves = work ? work : 1;
 		HIPD(xzk_malloc(&d_lit, (uint64_t)waves * (0x300ull << 4) * 2), "hipMalloc");
@@ -232,10 +328,46 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 		unsigned long long *d_mism = (unsigned long long *)((uint8_t *)d_misc + 64);
 		uint32_t *d_berr = (uint32_t *)((uint8_t *)d_misc + 4096);
 		HIPD(xzk_dec_units(d_xz, (const xzamd_dec_block *)d_blocks, nbk, (const xzamd_dec_unit *)d_units, units_cap,
-				(const uint32_t *)d_first, total_units, d_out, hist, (uint16_t *)d_lit, waves, d_counter, d_berr, st), "decode launch");
+				(const uint32_t *)d_first, total_units, dec_out, hist, (uint16_t *)d_lit, waves, d_counter, d_berr, st), "decode launch");
 		HIPD(xzk_d2h(h_err, d_berr, 4 * nb, st) || xzk_sync(st), "decode");
 		for (uint64_t b = 0; b < nb; ++b)
 			if (h_err[b]) FAILD(XZAMD_DATA_ERROR, "LZMA2 data (range coder / distances / chunk sizes)");
+		if (any_filtered) {
+			/* inverse stages, the filter next to LZMA2 first; an unfiltered Block of a mixed Stream is copied in stage 0 */
+			xzamd_unf_args ua;
+			memset(&ua, 0, sizeof(ua));
+			ua.blocks = (const xzamd_dec_block *)d_blocks;
+			ua.chains = (const xzamd_dec_chain *)d_chains;
+			ua.tile_first = (const uint32_t *)d_tiles;
+			ua.nblocks = nbk;
+			ua.t0 = (uint8_t *)d_t0; ua.t1 = (uint8_t *)d_t1; ua.out = d_out;
+			for (uint32_t k = 0; k < max_nf; ++k) {
+				uint64_t tiles = 0;
+				uint32_t kinds = 0;
+				for (uint64_t b = 0; b < nb; ++b) {
+					tile_first[b] = (uint32_t)tiles;
+					if (hc[b].n > k || (hc[b].n == 0 && k == 0)) {
+						const uint32_t kind = hc[b].n ? hc[b].f[hc[b].n - 1 - k] & 0xFFu : 0u;
+						tiles += (hb[b].usize + XZAMD_UNF_TILE - 1) / XZAMD_UNF_TILE;
+						if (hb[b].usize)
+							kinds |= kind == 3u ? XZAMD_UNF_DELTA : kind ? XZAMD_UNF_COPY | XZAMD_UNF_BCJ : XZAMD_UNF_COPY;
+					}
+				}
+				tile_first[nb] = (uint32_t)tiles;
+				if (tiles >= (1ull << 31)) FAILD(XZAMD_OPTIONS_ERROR, "Stream too large for the inverse filters");
+				if (tiles == 0) continue;
+				if ((kinds & XZAMD_UNF_DELTA) && !d_tsum) {
+					/* every later stage covers a subset of this stage's Blocks: its tiles fit */
+					HIPD(xzk_malloc(&d_tsum, tiles * XZAMD_UNF_ROW) || xzk_malloc(&d_tcarry, tiles * XZAMD_UNF_ROW), "hipMalloc");
+				}
+				ua.tile_sum = (uint8_t *)d_tsum; ua.tile_carry = (uint8_t *)d_tcarry;
+				ua.stage = k;
+				/* tile_first is rewritten for the next stage: the copy must have left the host buffer first */
+				HIPD(xzk_h2d(d_tiles, tile_first, 4 * (nb + 1), st) || xzk_sync(st), "h2d tiles");
+				HIPD(xzk_dec_unfilter(&ua, (uint32_t)tiles, kinds, st), "inverse filter launch");
+				count_(1);
+			}
+		}
 		/* Block checks over the decoded bytes */
 		if (check == XZAMD_CHECK_CRC32 || check == XZAMD_CHECK_CRC64) {
 			const uint32_t strip = 4096;
@@ -301,6 +433,14 @@ done:
 	if (d_strip) xzk_free(d_strip);
 	if (d_crc) xzk_free(d_crc);
 	if (d_sha) xzk_free(d_sha);
+	if (d_chains) xzk_free(d_chains);
+	if (d_tiles) xzk_free(d_tiles);
+	if (d_t0) xzk_free(d_t0);
+	if (d_t1) xzk_free(d_t1);
+	if (d_filt) xzk_free(d_filt);
+	if (d_tsum) xzk_free(d_tsum);
+	if (d_tcarry) xzk_free(d_tcarry);
+	free(hc); free(tile_first);
 	free(stored32);
 	free(index); free(hb); free(stored); free(h_crc); free(h_err); free(unit_first);
 	return rc;

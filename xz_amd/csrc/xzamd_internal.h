@@ -18,5 +18,9 @@ int xzamd_encode_finish_(xzamd_ctx *c, uint64_t *out_size);
 int xzamd_stored_blocks_host_(const uint8_t *in, uint64_t n, uint64_t block_size, int check,
 		uint8_t *out, uint64_t out_cap, uint64_t *out_size, xzamd_block_info *binfo, uint64_t binfo_cap, uint64_t *nblocks);
 
+/* test instrumentation of the device decoder: temporaries allocated for inverse filters, inverse-stage calls, forward-filter
+ * launches of verification decodes (process-wide counts) */
+void xzamd_debug_decode_counters_(uint64_t out[3]);
+
 double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt);   /* device work buffers per input byte of a batch */
 #endif

@@ -1,4 +1,4 @@
-/* stub_xzk.c -- TEST INFRASTRUCTURE ONLY: a CPU stand-in for the kernels_api.h layer (lzma_kernels.hip), so that the
+/* stub_xzk.c -- TEST INFRASTRUCTURE ONLY: a CPU stand-in for the kernels_api.h layer (the .hip units of xz_amd/csrc), so that the
  * plain-C host code of the product (xzamd_host.c: batch geometry, span plan bookkeeping, ordered layout, stored-Block
  * fallback, framing; xzamd_stream.c: the lzma_code state machine, worker threads, ordered job queue, timeouts) can
  * run under AddressSanitizer / UndefinedBehaviorSanitizer / ThreadSanitizer on a box without a GPU (SURVEY.md 5:

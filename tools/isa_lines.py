@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Static instruction mix of one kernel by source line, from `hipcc -S -gline-tables-only --cuda-device-only`.
-usage: tools/isa_lines.py file.s kernel-substring [first_line last_line]"""
+usage: tools/isa_lines.py file.s source.hip kernel-substring [first_line last_line]
+(source.hip: the unit file.s was compiled from, e.g. xz_amd/csrc/lzma_kernels.hip; its lines are quoted next to the counts)"""
 import re, sys, collections
-path, kern = sys.argv[1], sys.argv[2]
-lo = int(sys.argv[3]) if len(sys.argv) > 3 else 0
-hi = int(sys.argv[4]) if len(sys.argv) > 4 else 10**9
+path, srcpath, kern = sys.argv[1], sys.argv[2], sys.argv[3]
+lo = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+hi = int(sys.argv[5]) if len(sys.argv) > 5 else 10**9
 cnt = collections.defaultdict(lambda: collections.Counter())
 infn = False; line = 0
 def cls(op):
@@ -36,7 +37,7 @@ for ln, c in cnt.items():
         tot.update(c); rows.append((ln, c))
 print('total', dict(tot))
 rows.sort(key=lambda r: -(r[1]['salu'] + r[1]['vlane']))
-src = open('/root/repo/xz_amd/csrc/lzma_kernels.hip').read().split('\n') if len(sys.argv) <= 5 else []
+src = open(srcpath).read().split('\n')
 for ln, c in rows[:70]:
     s = src[ln - 1].strip()[:90] if src and ln - 1 < len(src) else ''
     print(f"{ln:5d} salu {c['salu']:4d} vlane {c['vlane']:3d} valu {c['valu']:4d} lds {c['lds']:3d} vmem {c['vmem']:3d} scr {c['scratch']:3d} br {c['br']:3d} wait {c['wait']:3d} | {s}")

@@ -19,15 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels_api.h"
+#include "wave.h"
+#include "bcj_rules.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ void wave_sync()
-{
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
 
 enum : uint32_t {      // error codes (xzamd_dec_block.error)
     DEC_OK = 0, DEC_BAD_CONTROL = 1, DEC_NEED_DICT_RESET = 2, DEC_NEED_PROPS = 3, DEC_BAD_PROPS = 4,
@@ -466,10 +461,7 @@ __global__ __launch_bounds__(256) void k_unf_copy(xzamd_unf_args a)
     }
 }
 
-__device__ __forceinline__ bool x86_is_op(uint32_t b) { return (b & 0xFEu) == 0xE8u; }
-__device__ __forceinline__ bool x86_ms(uint32_t b) { return b == 0u || b == 0xFFu; }
-
-// x86 (simple/x86.c:26-118, is_encoder = false).  The argument above k_x86_bcj (lzma_kernels.hip) holds for this
+// x86 (simple/x86.c:26-118, is_encoder = false).  The argument above k_x86_bcj (lzma_filters.hip) holds for this
 // direction word for word: every decision of the decoder reads its own INPUT only (the filtered bytes: a converted
 // operand is skipped, never read again), and (prev_mask, prev_pos) are void at a position with five bytes without
 // E8 / E9 in front of it.  So the owner of chunk k starts at the first such synchronisation point of its chunk and
@@ -537,29 +529,9 @@ __device__ void unf_x86(const uint8_t* __restrict__ b, uint8_t* __restrict__ o, 
 // re-encodes; an AUIPC in the special form: the real pair it restores) and jumps 2, 4, 6 or 8 bytes accordingly, reading
 // only bytes no earlier conversion wrote.  So the walk is cut into chunks by the rule of k_riscv_bcj: a position that
 // none of its three predecessors can jump over is examined by every walk.
-__device__ __forceinline__ uint32_t rv_rd32(const uint8_t* p)
-{
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
 __device__ __forceinline__ void rv_wr32(uint8_t* p, uint32_t v)
 {
     p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
-}
-__device__ __forceinline__ bool rv_not_pair(uint32_t auipc, uint32_t inst2) { return (((auipc << 8) ^ inst2) & 0xF8003u) != 3u; }
-__device__ __forceinline__ bool rv_special(uint32_t auipc) { return (auipc & 0x3FFFu) == 0x3117u && ((auipc >> 27) & 0x1Du) != 0; }
-__device__ __forceinline__ uint32_t rv_step(const uint8_t* b, uint32_t i, uint32_t limit)
-{
-    if (i > limit) return 2;
-    const uint32_t b0 = b[i];
-    if (b0 == 0xEFu) return (b[i + 1] & 0x0Du) ? 2u : 4u;
-    if ((b0 & 0x7Fu) != 0x17u) return 2;
-    const uint32_t inst = rv_rd32(b + i);
-    if (inst & 0xE80u) return rv_not_pair(inst, rv_rd32(b + i + 4)) ? 6u : 8u;
-    return rv_special(inst) ? 8u : 4u;
-}
-__device__ __forceinline__ bool rv_sync(const uint8_t* b, uint32_t i, uint32_t limit)
-{
-    return (i < 2 || rv_step(b, i - 2, limit) <= 2) && (i < 4 || rv_step(b, i - 4, limit) <= 4) && (i < 6 || rv_step(b, i - 6, limit) <= 6);
 }
 
 __device__ void unf_riscv(const uint8_t* __restrict__ b, uint8_t* __restrict__ o, uint32_t size, uint32_t k)

@@ -1,21 +1,24 @@
-// lzma_kernels.hip -- MI355X (gfx950 / CDNA4) device side of the LZMA2 Block encoder.
+// lzma_kernels.hip -- MI355X (gfx950 / CDNA4) device side of the LZMA2 Block encoder: the parse and encode kernels.
 //
-// Replaces, for a whole batch of .xz Blocks resident in HBM, what one worker
-// thread of the reference runs per Block (stream_encoder_mt.c:219-298):
+// The encoder replaces, for a whole batch of .xz Blocks resident in HBM, what one worker
+// thread of the reference runs per Block (stream_encoder_mt.c:219-298).  Stage by stage, with the unit each lives in:
 //
-//   lz/lz_encoder_mf.c      HC3/HC4 match finder      -> k_h2_* / k_hash_keys + radix sort + k_link_*
+//   lz/lz_encoder_mf.c      HC3/HC4 match finder      -> k_h2_* / k_hash_keys + radix sort + k_link_*         lzma_build.hip
 //                                                       (Block-global "sorted bucket" chains)
-//                                                       + wave-parallel candidate evaluation (do_round)
+//                                                       + wave-parallel candidate evaluation (do_round)      match_common.h
+//                                                       for every position (k_find_exact)                    lzma_find.hip
 //   lz/lz_encoder_mf.c      BT4 (presets 4-9)         -> suffix-neighbourhood finder: k_sa_* (suffix order of every
-//                                                       Block by radix sorts + rank doubling), k_find_sn
-//   lzma/lzma_encoder_optimum_fast.c    parser        -> fast parser block of span_encode_one (wave-uniform)
-//   lzma/lzma_encoder_optimum_normal.c  parser        -> optimum_window() (windowed DP, lane = length / candidate)
-//   lzma/lzma_encoder.c     symbol coder               -> encode_symbol()
-//   rangecoder/range_encoder.h  range coder            -> struct RC
-//   lzma/lzma2_encoder.c    chunk framing              -> span_encode_one epilogue
-//   simple/*.c, delta/      filters in front of LZMA2  -> k_x86_bcj, k_riscv_bcj, k_arm64_bcj, k_bcj_simple, k_delta
-//   check/crc64_fast.c, crc32, sha256.c                -> k_crc_strips / k_crc_fold, k_sha256_blocks
-//   block_encoder.c / stream_encoder_mt.c assembly     -> k_assemble (gather of span outputs)
+//                                                       Block by radix sorts + rank doubling)                lzma_build.hip
+//                                                       k_find_sn; span plan k_span_est / k_span_cut         lzma_find.hip
+//   lzma/lzma_encoder_optimum_fast.c    parser        -> fast parser block of span_encode_one (wave-uniform)  here
+//   lzma/lzma_encoder_optimum_normal.c  parser        -> optimum_window() (windowed DP, lane = length / candidate)  here
+//   lzma/lzma_encoder.c     symbol coder               -> encode_symbol()                                      here
+//   rangecoder/range_encoder.h  range coder            -> struct RC                                            here
+//   lzma/lzma2_encoder.c    chunk framing              -> span_encode_one epilogue                             here
+//   simple/*.c, delta/      filters in front of LZMA2  -> k_x86_bcj, k_riscv_bcj, k_arm64_bcj, k_bcj_simple, k_delta  lzma_filters.hip
+//   check/crc64_fast.c, crc32, sha256.c                -> k_crc_strips / k_crc_fold, k_sha256_blocks           lzma_filters.hip
+//   block_encoder.c / stream_encoder_mt.c assembly     -> k_assemble (gather of span outputs)                  here
+//   (HIP runtime calls of the plain-C host layer)      -> xzk_malloc ... xzk_mem_info                          hip_shims.hip
 //
 // Design: the sequential insert-then-search structures of the
 // reference are replaced by parse-independent ones built in parallel.  Hash
@@ -37,14 +40,13 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
 #include "kernels_api.h"
+#include "wave.h"
+#include "match_common.h"
 
 namespace {
 
-constexpr uint32_t MATCH_LEN_MAX = 273;
 constexpr uint32_t LITERAL = 0xFFFFFFFFu;
 constexpr uint32_t NO_DELTA = 0xFFFFFFFFu;
 
@@ -68,436 +70,6 @@ enum : uint32_t {
     P_TOTAL = P_LITERAL + (0x300 << 3)            // 7990
 };
 static_assert(P_TOTAL <= 8192, "model must fit the 16 KiB LDS slice");
-
-// Make LDS stores of some lanes visible to later LDS loads of other lanes of the same wavefront:
-// LDS hand-off between lanes of the wave.  DS instructions of one wave execute in issue order, so a
-// ds_write is visible to any later ds_read of the same wave without waiting; what has to be
-// prevented is the COMPILER moving accesses across the hand-off.  A compiler-only barrier: a fence
-// builtin would also drain vmcnt, i.e. wait for every prefetch in flight at each hand-off.
-__device__ __forceinline__ void wave_sync()
-{
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-// Sum over the 64 lanes on the DPP network (no LDS traffic): row-wise shifts, then the two row broadcasts; lane 63 has it.
-__device__ __forceinline__ uint32_t wave_sum_dpp(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);     // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);     // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);     // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);     // row_shr:8   -> lane 15 of a row = row sum
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, true);     // row_bcast:15 into rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, true);     // row_bcast:31 into rows 2, 3
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// A wave-uniform value the compiler must keep in a scalar register from here on (no instruction is emitted when it is
-// there already): without the pin a loop-carried uniform chain can end up on the vector ALU as a whole.
-__device__ __forceinline__ void pin_s(uint32_t& v) { asm volatile("" : "+s"(v)); }
-__device__ __forceinline__ void pin_s(uint64_t& v) { asm volatile("" : "+s"(v)); }
-__device__ __forceinline__ uint32_t lane_of(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, uni(l)); }
-
-// CRC32 table[0] entry for one byte (lz_encoder_hash.h:31-39 uses lzma_crc32_table[0]).
-__device__ __forceinline__ uint32_t crc_t0(uint32_t b)
-{
-    uint32_t r = b;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r = (r >> 1) ^ ((r & 1) ? 0xEDB88320u : 0u);
-    return r;
-}
-
-// ------------------------------------------------------------------------------------------
-// Match-finder structure build
-// ------------------------------------------------------------------------------------------
-
-// One thread per input byte: one of the hash keys of lz_encoder_hash.h:55-75 (which = 2: hash2,
-// 3: hash3 of HC4, 0: the main chain hash), prefixed with the Block number so one sort serves
-// every Block of the batch.  Positions with fewer than hash_bytes left in their Block are never
-// inserted by the reference (lz_encoder_mf.c:190-201 "pending"): they get the sentinel bucket
-// `nblocks`.  vals = iota (the position itself).
-__global__ __launch_bounds__(256) void k_hash_keys(const uint8_t* __restrict__ in, uint32_t n,
-        uint32_t block_size, uint32_t nblocks, uint32_t hash_bytes, uint32_t hash_mask, uint32_t hash_bits,
-        uint32_t which, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals)
-{
-    __shared__ uint32_t T[256];
-    T[threadIdx.x] = crc_t0(threadIdx.x);
-    __syncthreads();
-    const uint32_t kbits = which == 2 ? 10u : (which == 3 ? 16u : hash_bits);
-    const uint32_t need = hash_bytes;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride) {
-        const uint32_t b = g / block_size;
-        const uint32_t bend = min(n, (b + 1) * block_size);   // n < 2^31, no overflow
-        const uint32_t avail = bend - g;
-        uint32_t key = nblocks << kbits;
-        if (avail >= need) {
-            const uint32_t c0 = in[g], c1 = in[g + 1], c2 = in[g + 2];
-            const uint32_t temp = T[c0] ^ c1;
-            uint32_t h;
-            if (which == 2) h = temp & 0x3FF;
-            else if (which == 3) h = (temp ^ (c2 << 8)) & 0xFFFF;
-            else if (hash_bytes == 3) h = (temp ^ (c2 << 8)) & hash_mask;
-            else h = (temp ^ (c2 << 8) ^ (T[in[g + 3]] << 5)) & hash_mask;
-            key = (b << kbits) | h;
-        }
-        keys[g] = key;
-        vals[g] = g;
-    }
-}
-
-// After the stable sort by key_main: publish the bucket order.
-//   sorted_pos[i] = position | (first-of-bucket << 31)      rank[position] = i
-__global__ __launch_bounds__(256) void k_link_main(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-        uint32_t n, uint32_t* __restrict__ sorted_pos, uint32_t* __restrict__ rank)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t p = vals[i];
-        const uint32_t first = (i == 0 || keys[i - 1] != keys[i]) ? 0x80000000u : 0u;
-        sorted_pos[i] = p | first;
-        rank[p] = i;
-    }
-}
-
-// After the stable sort by key2 / key3 / key4: prev[position] = distance to the previous position of the same
-// bucket (the value the reference's hash head table holds when `position` is reached, expressed as delta),
-// 0 = none.
-// hash2 needs no sort: its table has 1024 entries per Block, so the "previous position with the same hash" is
-// found the way the reference does it -- a head table walked in text order -- with the Block cut into segments of
-// H2_SEG positions, one wavefront each:
-//   k_h2_last   last inserted position (+1) of every hash value inside the segment      (LDS table, ds_max)
-//   k_h2_scan   per Block: exclusive running maximum of those tables over its segments   (the carry-in heads)
-//   k_h2_prev   the segment again, 64 positions a step: a lane's predecessor is the highest lower lane of the
-//               step with the same hash (ten ballots give every lane its set of peers), else the table entry;
-//               the last lane of each peer set then updates the table.
-// Positions with fewer than hash_bytes left in their Block are not inserted and get 0 (they are never looked up).
-constexpr uint32_t H2_SEG = 65536;
-
-__device__ __forceinline__ uint32_t h2_of(const uint8_t* __restrict__ in, const uint32_t* T, uint32_t p)
-{
-    return (T[in[p]] ^ in[p + 1]) & 0x3FFu;
-}
-
-__global__ __launch_bounds__(64) void k_h2_last(const uint8_t* __restrict__ in, uint32_t n, uint32_t block_size,
-        uint32_t segs_per_block, uint32_t hash_bytes, uint32_t* __restrict__ seg_tab)
-{
-    __shared__ uint32_t T[256];
-    __shared__ uint32_t tab[1024];
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t i = lane; i < 256; i += 64) T[i] = crc_t0(i);
-    for (uint32_t i = lane; i < 1024; i += 64) tab[i] = 0;
-    const uint32_t b = blockIdx.x / segs_per_block, sg = blockIdx.x - b * segs_per_block;
-    const uint32_t bs = b * block_size;
-    const uint32_t bend = min(n, bs + block_size);
-    const uint32_t s0 = bs + sg * H2_SEG;
-    const uint32_t s1 = min(bend, s0 + H2_SEG);
-    wave_sync();
-    for (uint32_t x = s0 + lane; x < s1; x += 64)
-        if (bend - x >= hash_bytes) atomicMax(&tab[h2_of(in, T, x)], x + 1);
-    wave_sync();
-    uint32_t* out = seg_tab + (uint64_t)blockIdx.x * 1024;
-    for (uint32_t i = lane; i < 1024; i += 64) out[i] = tab[i];
-}
-
-__global__ __launch_bounds__(256) void k_h2_scan(uint32_t* __restrict__ seg_tab, uint32_t segs_per_block)
-{
-    // thread = (Block, hash value): exclusive running maximum along the Block's segments
-    const uint32_t b = blockIdx.x >> 2, h = ((blockIdx.x & 3) << 8) | threadIdx.x;
-    uint32_t* t = seg_tab + (uint64_t)b * segs_per_block * 1024 + h;
-    uint32_t run = 0;
-    for (uint32_t s = 0; s < segs_per_block; ++s) {
-        const uint32_t v = t[(uint64_t)s * 1024];
-        t[(uint64_t)s * 1024] = run;
-        run = max(run, v);
-    }
-}
-
-__global__ __launch_bounds__(64) void k_h2_prev(const uint8_t* __restrict__ in, uint32_t n, uint32_t block_size,
-        uint32_t segs_per_block, uint32_t hash_bytes, const uint32_t* __restrict__ seg_tab, uint32_t* __restrict__ prev2)
-{
-    __shared__ uint32_t T[256];
-    __shared__ uint32_t tab[1024];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t* carry = seg_tab + (uint64_t)blockIdx.x * 1024;
-    for (uint32_t i = lane; i < 256; i += 64) T[i] = crc_t0(i);
-    for (uint32_t i = lane; i < 1024; i += 64) tab[i] = carry[i];
-    const uint32_t b = blockIdx.x / segs_per_block, sg = blockIdx.x - b * segs_per_block;
-    const uint32_t bs = b * block_size;
-    const uint32_t bend = min(n, bs + block_size);
-    const uint32_t s0 = bs + sg * H2_SEG;
-    const uint32_t s1 = min(bend, s0 + H2_SEG);
-    const uint64_t below = (1ull << lane) - 1;
-    wave_sync();
-    for (uint32_t x0 = s0; x0 < s1; x0 += 64) {
-        const uint32_t x = x0 + lane;
-        const bool ins = x < s1 && bend - x >= hash_bytes;
-        const uint32_t h = ins ? h2_of(in, T, x) : 0u;
-        uint64_t peers = __builtin_amdgcn_ballot_w64(ins);
-#pragma unroll
-        for (uint32_t k = 0; k < 10; ++k) {
-            const uint64_t m = __builtin_amdgcn_ballot_w64(((h >> k) & 1u) != 0);
-            peers &= ((h >> k) & 1u) ? m : ~m;
-        }
-        const uint32_t head = tab[h];                       // head before this step
-        const uint64_t lower = peers & below;
-        uint32_t d = 0;
-        if (lower) d = lane - (63u - (uint32_t)__builtin_clzll(lower));
-        else if (head) d = x + 1 - head;
-        if (x < s1) prev2[x] = ins ? d : 0u;
-        wave_sync();
-        if (ins && (peers >> lane) == 1ull) tab[h] = x + 1;   // last lane of its peer set
-        wave_sync();
-    }
-}
-
-// The same distances, written in sorted order (d[i] belongs to position vals[i]).  A scattered 4-byte store
-// costs a whole sector and 1.4 G of them run at ~30 G/s; sorting the (position, distance) pairs back by
-// position (invert_perm below: two streaming radix passes and an LDS step) is more than twice as fast.
-__global__ __launch_bounds__(256) void k_link_prev_seq(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-        uint32_t n, uint32_t* __restrict__ d)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        d[i] = (i > 0 && keys[i - 1] == keys[i]) ? vals[i] - vals[i - 1] : 0u;
-}
-
-__global__ __launch_bounds__(256) void k_iota(uint32_t* __restrict__ v, uint32_t n)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) v[i] = i;
-}
-
-// Last step of an inversion (invert_perm below).  The (position, value) pairs arrive sorted by position >> 15;
-// the positions are a permutation of 0..n-1, so bucket b is exactly the pairs of positions [b << 15, (b + 1) << 15)
-// and sits in exactly those slots.  One workgroup per bucket places the values in LDS by the low 15 bits and
-// writes the 128 KiB out linearly: the last 15 key bits cost one read and one coalesced write instead of two
-// radix passes.  In place is fine (a bucket reads and writes the same slots, reads first).
-constexpr uint32_t INV_LOW = 15;
-__global__ __launch_bounds__(1024) void k_inv_low_u32(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-        uint32_t n, uint32_t* __restrict__ out)
-{
-    __shared__ uint32_t lds_inv[1u << INV_LOW];             // 128 KiB of the 160 KiB a CU has
-    const uint32_t base = blockIdx.x << INV_LOW;
-    const uint32_t cnt = min(n - base, 1u << INV_LOW);
-    for (uint32_t i = threadIdx.x; i < cnt; i += 1024) lds_inv[keys[base + i] & ((1u << INV_LOW) - 1)] = vals[base + i];
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += 1024) out[base + i] = lds_inv[i];
-}
-
-// 64-bit values: the two halves go to two arrays (out_lo, out_hi), one LDS round each
-__global__ __launch_bounds__(1024) void k_inv_low_u64(const uint32_t* __restrict__ keys, const uint64_t* __restrict__ vals,
-        uint32_t n, uint32_t* __restrict__ out_lo, uint32_t* __restrict__ out_hi)
-{
-    __shared__ uint32_t lds_inv[1u << INV_LOW];             // 128 KiB of the 160 KiB a CU has
-    const uint32_t base = blockIdx.x << INV_LOW;
-    const uint32_t cnt = min(n - base, 1u << INV_LOW);
-    for (uint32_t i = threadIdx.x; i < cnt; i += 1024) lds_inv[keys[base + i] & ((1u << INV_LOW) - 1)] = (uint32_t)vals[base + i];
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += 1024) out_lo[base + i] = lds_inv[i];
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += 1024) lds_inv[keys[base + i] & ((1u << INV_LOW) - 1)] = (uint32_t)(vals[base + i] >> 32);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += 1024) out_hi[base + i] = lds_inv[i];
-}
-
-// ------------------------------------------------------------------------------------------
-// Suffix order of every Block by its first 32 bytes (oracle: build_sa) -- the structure behind the
-// suffix-neighbourhood finder.  Order inside a Block: four 8-byte chunks compared as big-endian
-// numbers (bytes past the Block end read as zero, a chunk that starts past the end sorts lowest),
-// ties by position.  Built by stable LSD radix sorts (rocprim onesweep, HBM-bound):
-//   round 0   sort (chunk(p), p), then stably by Block number (so the slots of a Block are exactly
-//             its positions' range);
-//   round h   h = 8, 16: rank[p] = 1 + first slot of p's group of equal keys; sort by
-//             (rank[p], rank[p + h]) (0 = past the Block end): doubles the compared prefix.
-// Group starts come from a max-scan over "slot if the key differs from its left neighbour".
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sa_chunk_keys(const uint8_t* __restrict__ in, uint32_t n, uint32_t block_size,
-        uint64_t* __restrict__ keys, uint32_t* __restrict__ vals)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride) {
-        const uint32_t b = g / block_size;
-        const uint32_t bend = min(n, (b + 1) * block_size);
-        const uint32_t avail = bend - g;
-        uint64_t v = 0;
-        if (avail >= 8) {
-            uint64_t t;
-            __builtin_memcpy(&t, in + g, 8);
-            v = __builtin_bswap64(t);
-        } else {
-            for (uint32_t i = 0; i < avail; ++i) v |= (uint64_t)in[g + i] << (56 - 8 * i);
-        }
-        keys[g] = v;
-        vals[g] = g;
-    }
-}
-
-// grp[i] = i where the 64-bit key differs from its left neighbour (or, with block_size != 0, where a Block
-// starts: the slots of a Block are its positions' range), else 0 (input of the max-scan)
-__global__ __launch_bounds__(256) void k_sa_flags64(const uint64_t* __restrict__ keys, uint32_t n, uint32_t block_size,
-        uint32_t* __restrict__ grp)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const bool first = i != 0 && (keys[i] != keys[i - 1] || (block_size != 0 && i % block_size == 0));
-        grp[i] = first ? i : 0u;
-    }
-}
-
-// round 0, second step: pack (position, chunk group) as the value, Block number as the key
-__global__ __launch_bounds__(256) void k_sa_block_keys(const uint32_t* __restrict__ pos, const uint32_t* __restrict__ grp,
-        uint32_t n, uint32_t block_size, uint32_t* __restrict__ bkeys, uint64_t* __restrict__ bvals)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t p = pos[i];
-        bkeys[i] = p / block_size;
-        bvals[i] = (uint64_t)p | ((uint64_t)grp[i] << 32);
-    }
-}
-
-// after the Block sort: positions out, group flags from (Block, chunk group)
-__global__ __launch_bounds__(256) void k_sa_block_unpack(const uint32_t* __restrict__ bkeys, const uint64_t* __restrict__ bvals,
-        uint32_t n, uint32_t* __restrict__ pos, uint32_t* __restrict__ grp)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t v = bvals[i];
-        pos[i] = (uint32_t)v;
-        const bool first = i == 0 || bkeys[i] != bkeys[i - 1] || (uint32_t)(bvals[i - 1] >> 32) != (uint32_t)(v >> 32);
-        grp[i] = (first && i != 0) ? i : 0u;
-    }
-}
-
-// Slot order: rk[i] = (group start + 1, distance to the left neighbour inside the group or 0) of position pos[i].
-// The second word is a by-product of the sort round: inside a group of equal keys positions ascend, so the left
-// neighbour of a group member is the nearest earlier position with the same 8 (round 0) / 16 (round 1) bytes.
-// The pairs are then brought to position order (invert_perm): two arrays indexed by position.
-__global__ __launch_bounds__(256) void k_sa_rank_seq(const uint32_t* __restrict__ pos, const uint32_t* __restrict__ grp,
-        uint32_t n, uint2* __restrict__ rk)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t g = grp[i];
-        rk[i] = make_uint2(g + 1, g != i ? pos[i] - pos[i - 1] : 0u);
-    }
-}
-
-// the same for the rounds that only want the rank (sa_depth > 32)
-__global__ __launch_bounds__(256) void k_sa_rank_only_seq(const uint32_t* __restrict__ grp, uint32_t n, uint32_t* __restrict__ rk)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) rk[i] = grp[i] + 1;
-}
-
-// ---- rank doubling on the unresolved slots only -------------------------------------------------------------
-// After the 16-byte round most positions of ordinary data are alone in their group (text: 88 %, after 32 bytes
-// 99.95 %): their slot is final.  A round then only has to order the slots that still share a group with another one:
-//   k_sa_unres     u[i] = 1 when slot i lies in a group of >= 2 slots            (exclusive scan -> compact index)
-//   k_sa_compact   (key, position, slot) of the unresolved slots, in slot order; key = (rank, rank of p + h) as
-//                  k_sa_pair_keys_pos makes it
-//   radix sort of those m elements (stable: equal keys keep ascending positions, as in the full round)
-//   k_sa_newgrp    group starts of the sorted elements (max-scan over "slot where the key changes")
-//   k_sa_writeback the j-th sorted element goes to the j-th unresolved slot (the groups are contiguous slot ranges in
-//                  ascending order, so the sorted sequence enumerates them in place); position, group start and the
-//                  by-position rank of the moved elements are updated
-__global__ __launch_bounds__(256) void k_sa_unres(const uint32_t* __restrict__ grp, uint32_t n, uint32_t* __restrict__ u)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        u[i] = (grp[i] != i || (i + 1 < n && grp[i + 1] == i)) ? 1u : 0u;
-}
-
-__global__ void k_sa_count(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ grp, uint32_t n, uint32_t* __restrict__ count)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *count = idx[n - 1] + ((grp[n - 1] != n - 1) ? 1u : 0u);      // the last slot has no right neighbour
-}
-
-__global__ __launch_bounds__(256) void k_sa_compact(const uint32_t* __restrict__ pos, const uint32_t* __restrict__ grp,
-        const uint32_t* __restrict__ idx, const uint32_t* __restrict__ rank, uint32_t n, uint32_t block_size, uint32_t h,
-        uint32_t sbits, uint64_t* __restrict__ ckey, uint32_t* __restrict__ cval, uint32_t* __restrict__ cslot)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t g = grp[i];
-        if (!(g != i || (i + 1 < n && grp[i + 1] == i))) continue;
-        const uint32_t j = idx[i];
-        const uint32_t p = pos[i];
-        const uint32_t bs = (p / block_size) * block_size;
-        const uint32_t bend = min(n, bs + block_size);
-        const uint32_t second = p + h < bend ? rank[p + h] - bs : 0u;
-        ckey[j] = ((uint64_t)(g + 1) << sbits) | second;
-        cval[j] = p;
-        cslot[j] = i;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_sa_newgrp(const uint64_t* __restrict__ ckey, const uint32_t* __restrict__ cslot,
-        uint32_t m, uint32_t* __restrict__ gs)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride)
-        gs[j] = (j == 0 || ckey[j] != ckey[j - 1]) ? cslot[j] : 0u;
-}
-
-__global__ __launch_bounds__(256) void k_sa_writeback(const uint32_t* __restrict__ cval, const uint32_t* __restrict__ cslot,
-        const uint32_t* __restrict__ gs, uint32_t m, uint32_t* __restrict__ pos, uint32_t* __restrict__ grp,
-        uint32_t* __restrict__ rank)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) {
-        const uint32_t sl = cslot[j], p = cval[j], g = gs[j];
-        pos[sl] = p;
-        grp[sl] = g;
-        rank[p] = g + 1;
-    }
-}
-
-// By-product of a sorted round: inside a run of equal keys the positions ascend, so the left neighbour of a member is the
-// nearest earlier position of its group; d[position] = distance to it (0: first of its group).  A scatter of m elements.
-__global__ __launch_bounds__(256) void k_sa_prev_scatter(const uint64_t* __restrict__ key, const uint32_t* __restrict__ val,
-        uint32_t m, uint32_t* __restrict__ d)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) {
-        const uint32_t p = val[j];
-        d[p] = (j > 0 && key[j] == key[j - 1]) ? p - val[j - 1] : 0u;
-    }
-}
-
-// doubling key of every position, in position order: (rank[p], rank[p + h]) with 0 for a second half that
-// starts past the Block end; vals = iota.  The second rank is taken relative to the Block (sbits = bits of
-// block_size + 1), so the key is 31 + sbits bits wide instead of 62: one radix pass less for Blocks up to 32 MiB.  (The radix sort is stable and the members of a group ascend by
-// position in slot order too, so feeding it in position order gives the same result as slot order -- without
-// the random gather of rank[p + h].)
-__global__ __launch_bounds__(256) void k_sa_pair_keys_pos(const uint32_t* __restrict__ rank, uint32_t n, uint32_t block_size,
-        uint32_t h, uint32_t sbits, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
-        const uint32_t b = p / block_size;
-        const uint32_t bs = b * block_size;
-        const uint32_t bend = min(n, bs + block_size);
-        // the second half lies in the same Block, whose slots are [bs, bend): relative rank 1..block_size
-        const uint32_t second = p + h < bend ? rank[p + h] - bs : 0u;
-        keys[p] = ((uint64_t)rank[p] << sbits) | second;
-        vals[p] = p;
-    }
-}
-
-// final: sa[i] = position of slot i; slot[i] = i (sorted by position afterwards: sa_rank)
-__global__ __launch_bounds__(256) void k_sa_final_seq(const uint32_t* __restrict__ pos, uint32_t n,
-        uint32_t* __restrict__ sa, uint32_t* __restrict__ slot)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        sa[i] = pos[i];
-        slot[i] = i;
-    }
-}
 
 // ------------------------------------------------------------------------------------------
 // Range coder (rangecoder/range_encoder.h:136-263), coding directly instead of queueing.
@@ -581,233 +153,6 @@ struct RC {
         reset();
     }
 };
-
-// ------------------------------------------------------------------------------------------
-// Wave-cooperative byte comparison
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p)
-{
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-
-// Per-lane: length of the common prefix of in[q..] and in[x..], at most lim.  Lanes diverge.
-// 32 bytes per trip: every loop iteration is a dependent HBM/L2 round trip, so the trip count
-// (not the byte count) is what a long match costs.
-__device__ __forceinline__ uint32_t lane_cmplen(const uint8_t* __restrict__ in, uint32_t q, uint32_t x, uint32_t lim)
-{
-    uint32_t len = 0;
-    while (len + 32 <= lim) {
-        const uint8_t* a = in + q + len;
-        const uint8_t* b = in + x + len;
-        const uint64_t a0 = ld64(a), a1 = ld64(a + 8), a2 = ld64(a + 16), a3 = ld64(a + 24);
-        const uint64_t b0 = ld64(b), b1 = ld64(b + 8), b2 = ld64(b + 16), b3 = ld64(b + 24);
-        uint64_t d = a0 ^ b0;
-        if (d) return len + (uint32_t)(__builtin_ctzll(d) >> 3);
-        d = a1 ^ b1;
-        if (d) return len + 8 + (uint32_t)(__builtin_ctzll(d) >> 3);
-        d = a2 ^ b2;
-        if (d) return len + 16 + (uint32_t)(__builtin_ctzll(d) >> 3);
-        d = a3 ^ b3;
-        if (d) return len + 24 + (uint32_t)(__builtin_ctzll(d) >> 3);
-        len += 32;
-    }
-    while (len + 8 <= lim) {
-        const uint64_t d = ld64(in + q + len) ^ ld64(in + x + len);
-        if (d) return len + (uint32_t)(__builtin_ctzll(d) >> 3);
-        len += 8;
-    }
-    while (len < lim && in[q + len] == in[x + len]) ++len;
-    return len;
-}
-
-// Whole wave: extend a known common prefix `len` of in[a..], in[b..] up to lim (64 bytes/step).
-__device__ __forceinline__ uint32_t wave_cmplen(const uint8_t* __restrict__ in, uint32_t a, uint32_t b,
-        uint32_t len, uint32_t lim)
-{
-    const uint32_t lane = threadIdx.x;
-    while (len < lim) {
-        const uint32_t off = len + lane;
-        const bool mism = off >= lim || in[a + off] != in[b + off];
-        const uint64_t m = __ballot(mism);
-        if (m) { len += (uint32_t)__builtin_ctzll(m); break; }
-        len += 64;
-    }
-    return len < lim ? len : lim;
-}
-
-__device__ __forceinline__ uint32_t prefix_max_incl(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = __shfl_up(v, s);
-        if (lane >= (uint32_t)s) v = max(v, o);
-    }
-    return v;
-}
-
-// ------------------------------------------------------------------------------------------
-// One "round": everything lzma_mf_find() would report at position x (lz_encoder_mf.c:22-79,
-// HC3 :305-335, HC4 :366-413, chain walk :250-287) plus the four rep-match lengths at x.
-// Lane roles: 0 = hash2 candidate, 1 = hash3 candidate, 2 = own slot (bucket flag only),
-// 3..2+depth = chain candidates in chain order, 60..63 = rep0..rep3.
-// ------------------------------------------------------------------------------------------
-struct Round {
-    uint64_t mask;      // recorded matches, in matches[] order (ascending lane)
-    uint32_t L;         // per lane: recorded length (lanes 0..58), rep length (60..63)
-    uint32_t D;         // per lane: distance (zero based)
-    uint32_t longest;   // lzma_mf_find() return value (incl. the > nice_len extension)
-};
-
-struct Env {
-    const uint8_t* __restrict__ in;
-    const uint32_t* __restrict__ rank;
-    const uint32_t* __restrict__ sorted_pos;
-    const uint32_t* __restrict__ prev2;
-    const uint32_t* __restrict__ prev3;
-    uint32_t nice, depth, hb, cyclic;
-    uint32_t block_end;
-    uint32_t n_last;                            // last valid byte offset of the batch (prefetch clamp)
-    // match lists written by k_find_sn / k_find_exact (one 32-byte record per position), read by the list-driven parser
-    const uint16_t* __restrict__ mlen;
-    const uint32_t* __restrict__ mdist;
-    uint32_t packed;                            // lists are one u32 per entry: length << 23 | distance-1 (dict <= 8 MiB)
-};
-constexpr uint32_t LIST_K = 7;                // entries kept per position (the LIST_K longest)
-constexpr uint32_t LIST_W = 8;                // words per position: LIST_K entries + trailer (count | len2 of the two longest)
-constexpr uint32_t LEN2_MAX = 127;            // cap of the rep0 run recorded with the two longest entries
-
-// ------------------------------------------------------------------------------------------
-// Software prefetch of the parse-independent per-position data.  Rounds mostly visit consecutive
-// positions (lookahead of the fast parser, every node of an optimal-parser window), so while the
-// wave works on position x the loads for x+1 (chain slots) and x+2 (rank / prev links) are already
-// in flight: two of the three dependent HBM round trips of a round leave the critical path.
-// ------------------------------------------------------------------------------------------
-struct PreA { uint32_t rk, d2, d3; };
-struct Pre {
-    uint32_t pos;       // position (a, ent) belong to; `an` belongs to pos + 1
-    bool valid;
-    PreA a;
-    uint32_t ent;       // per lane: chain slot entry for this lane's role
-    PreA an;
-};
-
-__device__ __forceinline__ PreA load_a(const Env& e, uint32_t x)
-{
-    x = x < e.n_last ? x : e.n_last;
-    PreA a;
-    a.rk = e.rank[x];
-    a.d2 = e.prev2[x];
-    a.d3 = e.hb == 4 ? e.prev3[x] : 0;
-    return a;
-}
-
-__device__ __forceinline__ uint32_t load_ent(const Env& e, const PreA& a)
-{
-    const uint32_t lane = threadIdx.x;
-    uint32_t ent = 0x80000000u;                      // out of range == "bucket start"
-    const bool in_chain = lane >= 2 && lane <= 2 + e.depth;
-    if (in_chain && a.rk >= lane - 2) ent = e.sorted_pos[a.rk - (lane - 2)];
-    return ent;
-}
-
-__device__ __forceinline__ void fetch(const Env& e, Pre& P, uint32_t x, PreA& a, uint32_t& ent)
-{
-    if (!(P.valid && P.pos == x)) {                  // cold start: two dependent round trips
-        P.a = load_a(e, x);
-        P.ent = load_ent(e, P.a);
-        P.an = load_a(e, x + 1);
-    }
-    a = P.a;
-    ent = P.ent;
-    const PreA an = P.an;                            // issued one round ago
-    P.a = an;
-    P.ent = load_ent(e, an);                         // for x + 1, consumed next round
-    P.an = load_a(e, x + 2);
-    P.pos = x + 1;
-    P.valid = true;
-}
-
-template <bool REPS = true>
-__device__ __forceinline__ void do_round(const Env& e, Pre& P, uint32_t x, uint32_t end,
-        uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, Round& R)
-{
-    PreA pa;
-    uint32_t pent;
-    fetch(e, P, x, pa, pent);
-    const uint32_t lane = threadIdx.x;
-    const uint32_t avail = end - x;
-    const uint32_t buf_avail = avail < MATCH_LEN_MAX ? avail : MATCH_LEN_MAX;
-    uint32_t len_limit = avail;
-    bool mf_ok = true;
-    if (e.nice <= len_limit) len_limit = e.nice;
-    else if (len_limit < e.hb) mf_ok = false;            // "pending": no matches reported
-
-    uint32_t q = 0, lim = 0;
-    bool chain_valid = false;
-    if (mf_ok) {
-        const uint32_t d2 = pa.d2;
-        const uint32_t d3 = pa.d3;
-        if (lane == 0) {
-            if (d2 != 0 && d2 < e.cyclic) { q = x - d2; lim = len_limit; }
-        } else if (lane == 1) {
-            if (d3 != 0 && d3 != d2 && d3 < e.cyclic) { q = x - d3; lim = len_limit; }
-        }
-        const uint32_t ent = pent;
-        const bool in_chain = lane >= 2 && lane <= 2 + e.depth;
-        const uint64_t flags = __ballot(in_chain && (ent >> 31)) >> 2;   // bit j = flag of slot rank-j
-        if (lane >= 3 && in_chain) {
-            const uint32_t j = lane - 2;                 // candidate number 1..depth
-            const bool same_bucket = (flags & ((1ull << j) - 1)) == 0;
-            const uint32_t qp = ent & 0x7FFFFFFFu;
-            if (same_bucket && x - qp < e.cyclic) { chain_valid = true; q = qp; lim = len_limit; }
-        }
-    }
-    if (REPS && lane >= 60) {
-        const uint32_t rep = lane == 60 ? r0 : lane == 61 ? r1 : lane == 62 ? r2 : r3;
-        q = x - rep - 1;
-        lim = buf_avail;
-    }
-
-    uint32_t L = lane_cmplen(e.in, q, x, lim);
-    const uint32_t D = x - q - 1;
-
-    const uint32_t L0 = lane_of(L, 0), L1 = lane_of(L, 1);
-    const bool has2 = L0 >= 1;              // first byte equal => (by the hash) >= 2 bytes equal
-    const bool has3 = L1 >= 1;              // lane 1 only active for HC4
-    uint32_t best;
-    bool done;
-    if (e.hb == 4) {
-        best = has3 ? L1 : (has2 ? L0 : 1);
-        done = (has2 || has3) && best == len_limit;
-        if (best < 3) best = 3;
-    } else {
-        best = has2 ? L0 : 2;
-        done = has2 && best == len_limit;
-    }
-    const uint32_t X = chain_valid ? L : 0;
-    const uint32_t incl = prefix_max_incl(X);
-    uint32_t excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0;
-    bool rec = chain_valid && !done && X > max(best, excl);
-    if (lane == 0) { rec = has2; if (has2 && has3) L = 2; }
-    if (lane == 1) rec = has3;
-    R.mask = mf_ok ? __ballot(rec) : 0ull;
-    R.L = L;
-    R.D = D;
-    uint32_t longest = 0;
-    if (R.mask) {
-        const uint32_t top = 63 - (uint32_t)__builtin_clzll(R.mask);
-        longest = lane_of(L, top);
-        if (longest == e.nice) {
-            const uint32_t dist = lane_of(D, top);
-            longest = wave_cmplen(e.in, x, x - dist - 1, longest, buf_avail);
-        }
-    }
-    R.longest = longest;
-}
 
 // ------------------------------------------------------------------------------------------
 // LZMA symbol coder (lzma/lzma_encoder.c:23-263)
@@ -1210,37 +555,6 @@ __device__ __forceinline__ uint64_t rm_of(const RoundL& R, uint32_t i)
 __device__ __forceinline__ uint32_t lane_scatter(uint32_t dst, uint32_t v)
 {
     return (uint32_t)__builtin_amdgcn_ds_permute((int)(dst << 2), (int)v);
-}
-
-// ---- list-driven rounds ------------------------------------------------------------------------
-// The match finder is parse independent (find and skip both insert), so k_find_t runs it for every
-// position of the batch as a separate, fully parallel kernel.  The parser then streams the lists:
-// positions are visited strictly in order, so the record of x+1 is always in flight while x is
-// priced.  Only the four rep-match lengths depend on the parse; lanes 60..63 measure them here.
-// (the record in flight is kept as it was loaded -- one register for the packed form, two for the other -- and taken apart
-// when its round is worked out, not when it is loaded: it is live across the whole node in front)
-struct ListPre { uint32_t pos; bool valid; uint32_t v, l16; };
-
-// One 32-byte record per position (see k_find_sn): lanes 0..6 = entries, lane 7 = trailer.
-__device__ __forceinline__ void lists_load(const Env& e, uint32_t x, uint32_t& v, uint32_t& l16)
-{
-    const uint32_t lane = threadIdx.x;
-    x = x < e.n_last ? x : e.n_last;
-    const uint64_t base = (uint64_t)x * LIST_W + (lane & (LIST_W - 1));
-    v = e.mdist[base];                             // every lane loads (lanes >= LIST_W repeat the record): no exec masking
-    l16 = e.packed ? 0u : (uint32_t)e.mlen[base];
-}
-
-// lane LIST_K of `tr` holds the trailer
-__device__ __forceinline__ void lists_split(const Env& e, uint32_t v, uint32_t l16, uint32_t& sl, uint32_t& sd, uint32_t& tr)
-{
-    tr = v;
-    if (e.packed) {
-        sl = v >> 23; sd = v & 0x7FFFFFu;
-    } else {
-        sd = v;
-        sl = l16;
-    }
 }
 
 // The five byte rows of a round (lane = byte offset): the text at x and the four rep sources.  They can be issued as
@@ -3303,1134 +2617,9 @@ __global__ __launch_bounds__(64) void k_rc_chunks(xzamd_span_args a, uint32_t nc
 }
 
 // ------------------------------------------------------------------------------------------
-// Batch match finders: one wavefront per run of FIND_RUN consecutive positions.  Because find and
-// skip both insert (lz_encoder_mf.c:366-441), the matches of a position depend on the data only, so
-// they are computed for every position of the batch ahead of the (serial) parser, which streams
-// them.  Per position one 32-byte record: LIST_K entries sorted by length (length << 23 | distance-1
-// when the dictionary is <= 8 MiB, else distance-1 with the lengths in a u16 side array), the > nice_len
-// extension folded into the last one, and a trailer word
-//     count | len2(longest) << 8 | len2(second longest) << 16
-// where len2 = length of the rep0 run behind the byte that follows the match (the "match + literal +
-// rep0" edge of the parser, lzma_encoder_optimum_normal.c:728-790).
-// ------------------------------------------------------------------------------------------
-constexpr uint32_t FIND_RUN = 256;
-
-// bytes matched inside one 16-byte trip (16 = all)
-__device__ __forceinline__ uint32_t match16(const uint4& a, const uint4& b)
-{
-    const uint32_t d0 = a.x ^ b.x, d1 = a.y ^ b.y, d2 = a.z ^ b.z, d3 = a.w ^ b.w;
-    const uint32_t off = d0 ? 0u : d1 ? 4u : d2 ? 8u : 12u;
-    const uint32_t d = d0 ? d0 : d1 ? d1 : d2 ? d2 : d3;
-    return d ? off + ((uint32_t)__builtin_ctz(d) >> 3) : 16u;
-}
-
-// continue a compare whose first `len` bytes are known equal
-__device__ __forceinline__ uint32_t lane_cmplen16_from(const uint8_t* __restrict__ in, uint32_t q, uint32_t x, uint32_t len,
-        uint32_t lim)
-{
-    while (len + 16 <= lim) {
-        uint4 a, b;
-        __builtin_memcpy(&a, in + q + len, 16);
-        __builtin_memcpy(&b, in + x + len, 16);
-        const uint32_t m = match16(a, b);
-        len += m;
-        if (m < 16) return len;
-    }
-    while (len < lim && in[q + len] == in[x + len]) ++len;
-    return len;
-}
-
-// inclusive prefix maximum inside each half (32 lanes) of the wavefront
-__device__ __forceinline__ uint32_t prefix_max_half(uint32_t v)
-{
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false));   // row_shr:1
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false));   // row_shr:2
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false));   // row_shr:4
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false));   // row_shr:8
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false));   // row_bcast:15 -> rows 1, 3
-    return v;
-}
-
-struct SnArgs {
-    const uint8_t* __restrict__ in;
-    const uint32_t* __restrict__ sa;        // slot -> position (Block-major: the slots of a Block are its positions' range)
-    const uint32_t* __restrict__ sa_rank;   // position -> slot
-    const uint32_t* __restrict__ prev2;
-    const uint32_t* __restrict__ prev4;
-    const uint32_t* __restrict__ prev8;
-    const uint32_t* __restrict__ prev16;
-    const uint32_t* __restrict__ prev24;    // nearest earlier position with the same 24 / 32 bytes
-    const uint32_t* __restrict__ prev32;
-    // Which runs a launch covers: 0 = all; 1 = the runs that touch the first XZAMD_SEED_LEN bytes of a Block (workgroup =
-    // Block * SEED_RUNS + j); 2 = all the others.  The two-phase mode parses the seed pieces (k_parse_pieces phase 0)
-    // underneath launch 2.
-    uint32_t mode;
-};
-constexpr uint32_t SEED_RUNS = XZAMD_SEED_LEN / 256 + 1;
-constexpr uint32_t SN_WMAX = 5;
-
-// Suffix-neighbourhood finder (oracle: find_sn).  Both hot kernels of this path are bound by instruction
-// issue, not by memory, so the finder gives a position only the lanes it can use: a wavefront works on FOUR
-// positions at once, one per DPP row of 16 lanes, and everything "uniform per position" lives in vector
-// registers (the scalar unit only runs the loop).  Lane roles inside a row, t = lane & 15, slot r = own slot:
-//   t =  0..4   slots r-1 .. r-5   (left neighbours, nearest first)
-//   t =  5..9   slots r+1 .. r+5   (right neighbours, nearest first)
-//   t = 10 / 11 / 12   nearest previous position with equal hash2 / hash3 / hash4
-//   t = 13 / 14        nearest previous position with the same 8 / 16 bytes (by-products of the sort rounds)
-// A neighbour is eligible when it lies earlier in the same Block and inside the dictionary; it is a candidate
-// when it is more recent than every eligible neighbour nearer on its side ("recency record": exactly the
-// nodes BT4's descent would visit).  All candidates are compared with the text at x in parallel (16 bytes per
-// trip) and filtered by the Pareto rule with all-pairs compares inside the row (15 DPP row rotations).
-// Row r of the wavefront at x0 owns positions x0 + 64 r .. x0 + 64 r + 63.  The loop is software pipelined
-// three deep: while position i is compared and filtered, the first 16 bytes of every candidate of i + 1 and
-// the window of i + 2 are in flight.
-constexpr uint32_t SN_NONE = 0xFFFFFFFFu;     // "no neighbour in this lane" (positions are < 2^31)
-constexpr uint32_t ROW_RUN = FIND_RUN / 4;    // positions per row
-
-template <int N>
-__device__ __forceinline__ uint32_t row_ror(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x120 + N, 0xF, 0xF, false);    // row_ror:N
-}
-template <int N>
-__device__ __forceinline__ uint32_t row_shr(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + N, 0xF, 0xF, false);    // row_shr:N, 0 shifted in
-}
-
-// one all-pairs step: partner = the lane N places away (inside the row)
-template <int N>
-__device__ __forceinline__ void pareto_step(uint32_t dist, uint32_t Lok, uint32_t t, bool& dom, uint32_t& rank)
-{
-    const uint32_t dj = row_ror<N>(dist), Lj = row_ror<N>(Lok), tj = row_ror<N>(t);
-    const bool before = Lj != 0 && (dj < dist || (dj == dist && tj < t));      // partner is a candidate and sorts before me
-    dom = dom || (before && (Lj >= Lok || dj == dist));
-    rank += before ? 1u : 0u;
-}
-template <int N>
-__device__ __forceinline__ void count_step(uint32_t key, uint32_t t, uint32_t& idx)
-{
-    const uint32_t kj = row_ror<N>(key), tj = row_ror<N>(t);
-    idx += (kj < key || (kj == key && tj < t)) ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, uint16_t* __restrict__ mlen,
-        uint32_t* __restrict__ mdist)
-{
-    const uint32_t lane = threadIdx.x;
-    const uint32_t t = lane & 15, row = lane >> 4;
-    uint32_t run = blockIdx.x;
-    if (sn.mode == 1) {
-        const uint32_t b = blockIdx.x / SEED_RUNS, j = blockIdx.x - b * SEED_RUNS;
-        const uint32_t bs = b * a.block_size;
-        run = bs / FIND_RUN + j;
-        if ((uint64_t)run * FIND_RUN >= (uint64_t)bs + XZAMD_SEED_LEN || (uint64_t)run * FIND_RUN >= a.n) return;
-    } else if (sn.mode == 2) {
-        // a run belongs to launch 1 when it starts inside the seed region of its Block or reaches into the next Block
-        const uint32_t x0 = run * FIND_RUN;
-        const uint32_t b = x0 / a.block_size, bs = b * a.block_size;
-        const uint64_t be = (uint64_t)bs + a.block_size;
-        if (x0 < bs + XZAMD_SEED_LEN || ((uint64_t)x0 + FIND_RUN > be && be < a.n)) return;
-    }
-    const uint32_t xr0 = run * FIND_RUN + row * ROW_RUN;                 // first position of this row
-    const uint8_t* __restrict__ in = sn.in;
-    const uint32_t W = a.sa_window;
-    const uint32_t cyclic = a.dict_size + 1;
-    const uint32_t nice = a.nice_len;
-    const uint32_t n = a.n;
-    // lane roles
-    const bool left = t < 5, right = t >= 5 && t < 10;
-    const uint32_t k = left ? t : t - 5;
-    const bool win_lane = (left || right) && k < W;
-    // hash2 / hash4 heads and the 8- / 16-byte left neighbours.  (A hash3 head, lane 11, was measured to be worth
-    // nothing on text and 0.1 % on executables next to these: its sort and inversion are not built for this finder.)
-    // Lanes 11 / 15: the nearest earlier position with the same 24 / 32 bytes (by-products of the suffix-order rounds):
-    // between "same 16 bytes" and the suffix-order neighbours (which share the LONGEST prefixes, at any distance) these
-    // are the near candidates of medium length BT4's descent finds (measured through the oracle: -0.6 points of size on
-    // a SQLite file, -0.45 on C headers, -0.9 at 9e).
-    const bool hash_lane = t >= 10;
-    const uint32_t* __restrict__ hp = t == 10 ? sn.prev2 : t == 11 ? sn.prev24 : t == 12 ? sn.prev4 : t == 13 ? sn.prev8
-            : t == 14 ? sn.prev16 : sn.prev32;
-    const uint32_t hstride = 1u;
-    const uint32_t minlen = t == 10 ? 2u : 4u;
-    // masks for the prefix maximum inside a side (the right side must not look into the left one)
-    const bool sh1 = t != 0 && t != 5, sh2 = (left && t >= 2) || (right && t >= 7), sh4 = (left && t >= 4) || (right && t >= 9);
-
-    // geometry of the row's current position (per lane, equal inside a row): Block start / end.  The records are
-    // span independent (a match may run to the Block end): the spans are cut from these lists afterwards
-    // (k_span_est / k_span_cut) and the parser clamps what it reads to its span (round_lists).
-    uint32_t g_bs, g_be;
-    {
-        const uint32_t p = xr0 < n ? xr0 : 0u;
-        const uint32_t blk = p / a.block_size;
-        g_bs = blk * a.block_size;
-        g_be = min(n, g_bs + a.block_size);
-    }
-    auto geo_next = [&](uint32_t& bs, uint32_t& be, uint32_t p) {      // (bs, be) of p - 1 -> of p
-        const bool nb = p >= be;
-        bs = nb ? be : bs;
-        be = nb ? min(n, be + a.block_size) : be;
-    };
-    auto clampp = [&](uint32_t p) -> uint32_t { return p < n ? p : n - 1; };
-    // neighbour of this lane for position p with rank r inside Block [bs, be)
-    auto window = [&](uint32_t r, uint32_t bs, uint32_t be, bool live) -> uint32_t {
-        const int32_t slot = right ? (int32_t)(r + 1 + k) : (int32_t)r - 1 - (int32_t)k;
-        const bool inb = live && win_lane && slot >= (int32_t)bs && slot < (int32_t)be;
-        return inb ? sn.sa[slot] : SN_NONE;
-    };
-    auto candidate = [&](uint32_t p, uint32_t wq, uint32_t hw, uint32_t& q, bool& valid) {
-        const bool elig = wq != SN_NONE && wq < p && p - wq < cyclic;
-        const uint32_t v = elig ? wq + 1 : 0u;
-        uint32_t pm = v;
-        { const uint32_t o = row_shr<1>(pm); pm = max(pm, sh1 ? o : 0u); }
-        { const uint32_t o = row_shr<2>(pm); pm = max(pm, sh2 ? o : 0u); }
-        { const uint32_t o = row_shr<4>(pm); pm = max(pm, sh4 ? o : 0u); }
-        const uint32_t o1 = row_shr<1>(pm);
-        const uint32_t ex = sh1 ? o1 : 0u;
-        valid = elig && v > ex;
-        q = elig ? wq : 0u;
-        // The six hash / prefix lanes often name the same position (the nearest earlier position with the same 8 bytes is
-        // usually also the one with the same 16, 24, 32): the candidate stays in the lowest of those lanes only -- which is
-        // the one the Pareto rule below would keep -- and the others do not fetch its bytes again.  (hw is 0 in the
-        // window lanes; computed by every lane so that the row shifts see all their source lanes.)
-        bool dup = false;
-        { const uint32_t o = row_shr<1>(hw); dup = dup || (t >= 11 && o == hw); }
-        { const uint32_t o = row_shr<2>(hw); dup = dup || (t >= 12 && o == hw); }
-        { const uint32_t o = row_shr<3>(hw); dup = dup || (t >= 13 && o == hw); }
-        { const uint32_t o = row_shr<4>(hw); dup = dup || (t >= 14 && o == hw); }
-        { const uint32_t o = row_shr<5>(hw); dup = dup || (t >= 15 && o == hw); }
-        if (hash_lane) {
-            valid = hw != 0 && hw < cyclic && hw <= p && !dup;
-            q = valid ? p - hw : 0u;
-        }
-    };
-    auto load16 = [&](uint32_t off) -> uint4 {
-        uint4 v;
-        __builtin_memcpy(&v, in + off, 16);
-        return v;
-    };
-
-    // ---- prologue: positions i = 0, 1, 2 of the row
-    const uint32_t xend = min(n, xr0 + ROW_RUN);                          // this row's positions: [xr0, xend)
-    uint32_t g1_bs = g_bs, g1_be = g_be;                                  // geometry of x + 1
-    geo_next(g1_bs, g1_be, xr0 + 1);
-    uint32_t g2_bs = g1_bs, g2_be = g1_be;                                // geometry of x + 2
-    geo_next(g2_bs, g2_be, xr0 + 2);
-    uint32_t rk1 = sn.sa_rank[clampp(xr0 + 1)];
-    uint32_t rk2 = sn.sa_rank[clampp(xr0 + 2)];
-    uint32_t hw1 = hash_lane ? hp[hstride * clampp(xr0 + 1)] : 0u;
-    uint32_t w1 = window(rk1, g1_bs, g1_be, xr0 + 1 < xend);
-    uint32_t q0; bool v0;
-    {
-        const uint32_t rk0 = sn.sa_rank[clampp(xr0)];
-        const uint32_t hw0 = hash_lane ? hp[hstride * clampp(xr0)] : 0u;
-        candidate(xr0, window(rk0, g_bs, g_be, xr0 < xend), hw0, q0, v0);
-        if (!(xr0 < xend)) v0 = false;
-    }
-    bool pf0 = xr0 + 16 <= n;
-    uint4 A0 = make_uint4(0, 0, 0, 0), B0 = A0;
-    if (pf0) { A0 = load16(q0); B0 = load16(xr0); }
-
-    uint32_t macc = 0;
-    uint32_t i = 0;
-    for (; i < ROW_RUN; ++i) {
-        const uint32_t x = xr0 + i;
-        if (__builtin_amdgcn_readfirstlane((int)(blockIdx.x * FIND_RUN + i)) >= (int)n) break;   // every row is past the end
-        // stage 0: window of x + 2 (its rank arrived last iteration), rank of x + 3, hash word of x + 2
-        const uint32_t w2 = window(rk2, g2_bs, g2_be, x + 2 < xend);
-        const uint32_t rk3 = sn.sa_rank[clampp(x + 3)];
-        const uint32_t hw2 = hash_lane ? hp[hstride * clampp(x + 2)] : 0u;
-        // stage 1: candidates of x + 1 and their first 16 bytes
-        uint32_t q1; bool v1;
-        candidate(x + 1, w1, hw1, q1, v1);
-        if (!(x + 1 < xend)) { v1 = false; q1 = 0; }
-        const bool pf1 = x + 1 + 16 <= n;
-        uint4 A1 = A0, B1 = B0;
-        if (pf1) { A1 = load16(q1); B1 = load16(x + 1); }
-        // stage 2: position x
-        uint32_t mval = 0;                                  // this position's 16-bit summary for the span plan (top lane)
-        if (x < xend) {
-            const uint32_t q = q0;
-            const bool valid = v0;
-            const uint32_t avail = g_be - x;
-            const uint32_t buf_avail = avail < MATCH_LEN_MAX ? avail : MATCH_LEN_MAX;
-            const uint32_t len_limit = nice <= avail ? nice : avail;
-            const bool mf_ok = nice <= avail || avail >= 4;    // "pending": nothing is reported (lz_encoder_mf.c:190-201)
-            const uint64_t rec_base = (uint64_t)x * LIST_W;
-            const uint32_t lim = (valid && mf_ok) ? len_limit : 0u;
-            uint32_t L;
-            if (pf0) {
-                const uint32_t m = match16(A0, B0);
-                L = m < lim ? m : lim;
-                if (m == 16 && lim > 16) L = lane_cmplen16_from(in, q, x, 16, lim);
-            } else {
-                L = lane_cmplen16_from(in, q, x, 0, lim);
-            }
-            const bool ok = lim != 0 && L >= minlen;
-            const uint32_t dist = x - q;                        // delta >= 1 on ok lanes
-            const uint32_t Lok = ok ? L : 0u;
-            // Pareto set inside the row: drop a candidate when another one sorts before it (closer, or the same
-            // position in a lower lane) and is at least as long; rank = candidates sorting before me
-            bool dom = false;
-            uint32_t rank = 0;
-            pareto_step<1>(dist, Lok, t, dom, rank); pareto_step<2>(dist, Lok, t, dom, rank); pareto_step<3>(dist, Lok, t, dom, rank);
-            pareto_step<4>(dist, Lok, t, dom, rank); pareto_step<5>(dist, Lok, t, dom, rank); pareto_step<6>(dist, Lok, t, dom, rank);
-            pareto_step<7>(dist, Lok, t, dom, rank); pareto_step<8>(dist, Lok, t, dom, rank); pareto_step<9>(dist, Lok, t, dom, rank);
-            pareto_step<10>(dist, Lok, t, dom, rank); pareto_step<11>(dist, Lok, t, dom, rank); pareto_step<12>(dist, Lok, t, dom, rank);
-            pareto_step<13>(dist, Lok, t, dom, rank); pareto_step<14>(dist, Lok, t, dom, rank); pareto_step<15>(dist, Lok, t, dom, rank);
-            const bool keep = ok && !dom;
-            // index among the kept entries in distance (= length) order, and their number
-            const uint32_t key = keep ? rank : 0xFFu;
-            uint32_t kidx = 0;
-            count_step<1>(key, t, kidx); count_step<2>(key, t, kidx); count_step<3>(key, t, kidx); count_step<4>(key, t, kidx);
-            count_step<5>(key, t, kidx); count_step<6>(key, t, kidx); count_step<7>(key, t, kidx); count_step<8>(key, t, kidx);
-            count_step<9>(key, t, kidx); count_step<10>(key, t, kidx); count_step<11>(key, t, kidx); count_step<12>(key, t, kidx);
-            count_step<13>(key, t, kidx); count_step<14>(key, t, kidx); count_step<15>(key, t, kidx);
-            const uint64_t kmask = __ballot(keep);
-            const uint32_t cnt = (uint32_t)__builtin_popcount((uint32_t)(kmask >> (lane & 48)) & 0xFFFFu);
-            const bool top = keep && kidx + 1 == cnt, second = keep && kidx + 2 == cnt;
-            uint32_t len_out = L;
-            if (top && L == nice) len_out = lane_cmplen16_from(in, q, x, L, buf_avail);      // > nice_len extension
-            // rep0 run behind the byte after the match, for the two longest entries
-            uint32_t l2 = 0;
-            if ((top || second) && len_out + 1 < avail) {
-                const uint32_t lim2 = min(avail, len_out + 1 + LEN2_MAX);
-                l2 = lane_cmplen16_from(in, q, x, len_out + 1, lim2) - (len_out + 1);
-            }
-            const uint32_t drop = cnt > LIST_K ? cnt - LIST_K : 0;
-            if (keep && kidx >= drop) {
-                const uint64_t o = rec_base + (kidx - drop);
-                if (a.list_packed) {
-                    mdist[o] = (len_out << 23) | (dist - 1);
-                } else {
-                    mlen[o] = (uint16_t)len_out;
-                    mdist[o] = dist - 1;
-                }
-            }
-            // trailer: count | len2(longest) << 8 | len2(second) << 16, written bytewise by the lanes that know
-            uint8_t* tr = reinterpret_cast<uint8_t*>(mdist + rec_base + LIST_K);
-            if (cnt == 0) {
-                if (t == 0) mdist[rec_base + LIST_K] = 0;
-            } else {
-                if (top) {
-                    *reinterpret_cast<uint16_t*>(tr) = (uint16_t)((cnt - drop) | (l2 << 8));
-                    tr[3] = 0;
-                    if (cnt == 1) tr[2] = 0;
-                    // what the span plan's walk needs of this position (k_span_est), 2 bytes instead of the 32-byte record
-                    mval = len_out | ((dist > 1 ? 32u - (uint32_t)__builtin_clz(dist - 1) : 0u) << 9);
-                }
-                if (second) tr[2] = (uint8_t)l2;
-            }
-        }
-        // the summaries of 16 consecutive positions of a row are collected in its 16 lanes and stored together
-        // (a 2-byte store per position from one lane per row costs as much as the whole 32-byte record)
-        {
-            uint32_t rv = mval;
-            rv |= row_ror<1>(rv); rv |= row_ror<2>(rv); rv |= row_ror<4>(rv); rv |= row_ror<8>(rv);
-            macc = t == (i & 15u) ? rv : macc;
-            if ((i & 15u) == 15u) {
-                const uint32_t px = xr0 + (i & ~15u) + t;
-                if (px < xend) a.mtop[px] = (uint16_t)macc;
-            }
-        }
-        // shift the pipeline
-        q0 = q1; v0 = v1; pf0 = pf1; A0 = A1; B0 = B1;
-        w1 = w2; hw1 = hw2;
-        rk2 = rk3;
-        g_bs = g1_bs; g_be = g1_be;
-        g1_bs = g2_bs; g1_be = g2_be;
-        geo_next(g2_bs, g2_be, x + 3);
-    }
-    if (i & 15u) {                                          // the loop ended inside a group of 16 (end of the batch)
-        const uint32_t px = xr0 + (i & ~15u) + t;
-        if (t < (i & 15u) && px < xend) a.mtop[px] = (uint16_t)macc;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Cost-balanced spans (oracle: est_chunk / plan_spans).  A wavefront needs one step per position the optimal
-// parser visits, and positions covered by a match of nice_len bytes or more are not visited; a state reset costs a
-// few hundred bytes of model learning whatever the data.  So spans are cut by estimated parser work instead of
-// input bytes: the spans of a launch take about equally long whatever they hold, and highly compressible data
-// gets the long spans its small output needs.
-//   k_span_est   one thread per chunk of XZAMD_EST_CHUNK positions: a walk over the match lists.  A position whose
-//                longest match reaches nice_len costs EST_LONG units and the walk jumps over the match, any other
-//                position one unit; alongside, a greedy-parse estimate of the coded size in bits.
-//   k_span_cut   one wavefront per Block: k = max(1, work of the Block / target) spans of equal estimated work.
-// ------------------------------------------------------------------------------------------
-constexpr uint32_t EST_LONG = 4;
-
-__global__ __launch_bounds__(256) void k_span_est(xzamd_span_args a, uint32_t nblocks, uint32_t cpb,
-        uint32_t* __restrict__ est, unsigned long long* __restrict__ totals)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t nch = nblocks * cpb;
-    if (t >= nch) return;
-    const uint32_t b = t / cpb, c = t - b * cpb;
-    const uint32_t bs = b * a.block_size;
-    const uint32_t be = min(a.n, bs + a.block_size);
-    const uint64_t c0_ = (uint64_t)bs + (uint64_t)c * XZAMD_EST_CHUNK;
-    uint32_t w = 0, bits = 0;
-    if (c0_ < be) {
-        const uint32_t c0 = (uint32_t)c0_;
-        const uint32_t c1 = be - c0 < XZAMD_EST_CHUNK ? be : c0 + XZAMD_EST_CHUNK;
-        uint32_t x = c0, gnext = c0;
-        uint32_t cb = 0xFFFFFFFFu;                       // eight summaries at a time (16 bytes) through registers
-        uint4 buf = make_uint4(0, 0, 0, 0);
-        while (x < c1) {
-            const uint32_t base = x & ~7u;
-            if (base != cb) { buf = *reinterpret_cast<const uint4*>(a.mtop + base); cb = base; }
-            const uint32_t k = x & 7u;
-            const uint32_t wv = k < 2 ? buf.x : k < 4 ? buf.y : k < 6 ? buf.z : buf.w;
-            const uint32_t v = (k & 1u) ? wv >> 16 : wv & 0xFFFFu;
-            const uint32_t len = v & 0x1FFu, bl = v >> 9;          // bl <= 7 <=> zero-based distance < 128
-            if (x >= gnext) {
-                if (len >= 3 || (len == 2 && bl <= 7)) {
-                    bits += 14 + bl;
-                    gnext = x + len;
-                } else {
-                    bits += 6;
-                    gnext = x + 1;
-                }
-            }
-            if (len >= a.nice_len) { w += EST_LONG; x += len; }
-            else { w += 1; x += 1; }
-        }
-        atomicAdd(&totals[b], (unsigned long long)w);
-        atomicAdd(&totals[nblocks], (unsigned long long)w);
-    }
-    est[t] = w;
-    est[nch + t] = bits;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = __shfl_up(v, s);
-        if (lane >= (uint32_t)s) v += o;
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(64) void k_span_cut(xzamd_span_args a, uint32_t nblocks, uint32_t cpb,
-        const uint32_t* __restrict__ est, unsigned long long* __restrict__ totals, uint32_t* __restrict__ span_tab,
-        uint32_t* __restrict__ span_cnt, uint32_t cost_min, uint32_t bits_min, uint32_t min_len,
-        uint32_t* __restrict__ enc_tab, uint32_t* __restrict__ enc_cnt, uint32_t* __restrict__ span_key)
-{
-    const uint32_t lane = threadIdx.x;
-    const uint32_t b = blockIdx.x;
-    const uint32_t nch = nblocks * cpb;
-    const uint32_t bs = b * a.block_size;
-    const uint32_t be = min(a.n, bs + a.block_size);
-    const uint32_t m = (be - bs + XZAMD_EST_CHUNK - 1) / XZAMD_EST_CHUNK;      // chunks of this Block
-    // Work target of a span: cost_min, whatever the batch or the GPU -- the plan (and with it the output) of a Block is
-    // a function of the Block and the options alone.
-    const unsigned long long T = cost_min;
-    if (b == 0 && lane == 0) totals[nblocks + 1] = T;
-    const uint32_t* wk = est + (uint64_t)b * cpb;
-    const uint32_t* bt = est + nch + (uint64_t)b * cpb;
-    // two-phase: the first XZAMD_SEED_LEN bytes are the seed piece and the plan covers the rest
-    const bool two = a.enc_bits != 0;
-    const uint32_t seed_chunks = two && be - bs > XZAMD_SEED_LEN ? XZAMD_SEED_LEN / XZAMD_EST_CHUNK : 0u;
-    // spans of this Block: total / T of equal estimated work, but no more than its estimated coded size allows at
-    // bits_min per span (highly compressible Blocks get fewer, longer spans)
-    unsigned long long total = 0, total_bits = 0, all_bits = 0;
-    for (uint32_t c0 = 0; c0 < m; c0 += 64) {
-        const uint32_t c = c0 + lane;
-        const uint32_t vb = c < m ? bt[c] : 0u, vw = c < m ? wk[c] : 0u;
-        const bool planned = c >= seed_chunks;
-        all_bits += lane_of(wave_incl_sum(vb), 63);
-        total_bits += lane_of(wave_incl_sum(planned ? vb : 0u), 63);
-        total += lane_of(wave_incl_sum(planned ? vw : 0u), 63);
-    }
-    unsigned long long k = total / T;
-    if (bits_min) {
-        // (round 5's growth of bits_min on highly compressible Blocks is gone: oracle plan_spans_ex)
-        const unsigned long long kb = total_bits / (unsigned long long)bits_min;
-        if (kb < k) k = kb;
-    }
-    if (k == 0) k = 1;
-    const unsigned long long Tb = (total + k - 1) / k;
-    // encode spans (two-phase): ke of about equal estimated coded size, each closed at a piece end
-    unsigned long long ke = two ? all_bits / a.enc_bits : 1ull;
-    if (ke > (be - bs) / XZAMD_ENC_MIN_LEN) ke = (be - bs) / XZAMD_ENC_MIN_LEN;
-    if (ke == 0) ke = 1;
-    const unsigned long long Eb = (all_bits + ke - 1) / ke;
-    uint32_t* tab = span_tab + 2ull * b * a.max_spb;
-    uint32_t* etab = two ? enc_tab + 2ull * b * a.max_esb : nullptr;
-    uint32_t ns = 1, start = 0;                       // spans so far, first chunk of the open span
-    uint32_t ne = 1, estart = 0;                      // encode spans so far, first chunk of the open one
-    unsigned long long carry_w = 0;                   // estimated work of the open span in front of the window
-    unsigned long long carry_b = 0;                   // estimated bits of the open encode span in front of the window
-    if (lane == 0) { tab[0] = bs; if (two) etab[0] = bs; }
-    for (uint32_t c0 = 0; c0 < m; c0 += 64) {
-        const uint32_t c = c0 + lane;
-        const uint32_t pw = wave_incl_sum(c < m ? wk[c] : 0u);
-        const uint32_t pb = two ? wave_incl_sum(c < m ? bt[c] : 0u) : 0u;
-        uint32_t subw = 0;                            // window sum up to the last cut inside the window
-        uint32_t subb = 0;                            // the same for the bits, up to the last encode cut
-        for (;;) {
-            const unsigned long long accw = carry_w + (pw - subw);
-            const unsigned long long len = (unsigned long long)(c + 1 - start) * XZAMD_EST_CHUNK;
-            const bool cut = c + 1 < m && c >= start && ns < a.max_spb
-                    && (len >= XZAMD_SPAN_MAX || (accw >= Tb && len >= min_len) || c + 1 == seed_chunks);
-            const uint64_t mask = __builtin_amdgcn_ballot_w64(cut);
-            if (!mask) break;
-            const uint32_t L = (uint32_t)__builtin_ctzll(mask);
-            start = c0 + L + 1;
-            const unsigned long long closed = carry_w + (lane_of(pw, L) - subw);      // estimated work of the span just closed
-            subw = lane_of(pw, L);
-            carry_w = 0;
-            const uint32_t p = bs + start * XZAMD_EST_CHUNK;
-            if (lane == 0) {
-                tab[2 * ns - 1] = p;                  // end of the span just closed
-                tab[2 * ns] = p;
-                // launch-order key: heaviest first (ascending sort of ~work); unused slots keep 0xFFFFFFFF = last
-                span_key[(uint64_t)b * a.max_spb + ns - 1] = ~(uint32_t)min(closed ? closed : 1ull, 0xFFFFFFFEull);
-            }
-            ++ns;
-            if (two) {
-                const unsigned long long accb = carry_b + (lane_of(pb, L) - subb);
-                if (accb >= Eb && (unsigned long long)(start - estart) * XZAMD_EST_CHUNK >= XZAMD_ENC_MIN_LEN && ne < a.max_esb) {
-                    if (lane == 0) { etab[2 * ne - 1] = p; etab[2 * ne] = p; }
-                    ++ne;
-                    estart = start;
-                    subb = lane_of(pb, L);
-                    carry_b = 0;
-                }
-            }
-        }
-        carry_w += lane_of(pw, 63) - subw;
-        carry_b += lane_of(pb, 63) - subb;
-    }
-    if (lane == 0) {
-        tab[2 * ns - 1] = be;
-        span_cnt[b] = ns;
-        span_key[(uint64_t)b * a.max_spb + ns - 1] = ~(uint32_t)min(carry_w ? carry_w : 1ull, 0xFFFFFFFEull);
-        if (two) { etab[2 * ne - 1] = be; enc_cnt[b] = ne; }
-    }
-}
-
-// Where the first part of every piece ends (oracle: part_end_of): behind the 4 KiB chunk at which an eighth of the piece's
-// estimated work has been seen, at least XZAMD_PART_MIN bytes; the seed piece's part is the whole of it.  One thread per piece slot.
-__global__ __launch_bounds__(256) void k_part_ends(xzamd_span_args a, uint32_t nblocks, uint32_t cpb, const uint32_t* __restrict__ est,
-        uint32_t* __restrict__ part_tab)
-{
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= nblocks * a.max_spb) return;
-    const uint32_t blk = slot / a.max_spb, k = slot - blk * a.max_spb;
-    if (k >= a.span_cnt[blk]) return;
-    const uint32_t bs = blk * a.block_size;
-    const uint32_t s0 = a.span_tab[2 * slot], pe = a.span_tab[2 * slot + 1];
-    uint32_t end = pe;
-    if (k != 0 && pe - s0 > XZAMD_PART_MIN) {
-        const uint32_t* wk = est + (uint64_t)blk * cpb;
-        const uint32_t c0 = (s0 - bs) / XZAMD_EST_CHUNK, c1 = (pe - bs + XZAMD_EST_CHUNK - 1) / XZAMD_EST_CHUNK;
-        unsigned long long total = 0, acc = 0;
-        for (uint32_t c = c0; c < c1; ++c) total += wk[c];
-        const unsigned long long target = (total + 7) / 8;
-        for (uint32_t c = c0; c < c1; ++c) {             // the chunk boundary nearest to where the eighth is reached
-            const uint64_t b64 = (uint64_t)bs + (uint64_t)c * XZAMD_EST_CHUNK;
-            if (acc + wk[c] / 2 >= target && b64 >= (uint64_t)s0 + XZAMD_PART_MIN) { end = (uint32_t)b64; break; }
-            acc += wk[c];
-        }
-    }
-    part_tab[slot] = end;
-}
-
-// Exact HC3/HC4 finder in list form (optimal parser over the reference's match finder; test
-// configuration).  Same record layout, len2 = 0.
-__global__ __launch_bounds__(64) void k_find_exact(xzamd_span_args a, uint16_t* __restrict__ mlen,
-        uint32_t* __restrict__ mdist)
-{
-    const uint32_t lane = threadIdx.x;
-    const uint32_t x0 = blockIdx.x * FIND_RUN;
-    if (x0 >= a.n) return;
-    const uint32_t x1 = min(a.n, x0 + FIND_RUN);
-    Env e;
-    e.in = a.in; e.rank = a.rank; e.sorted_pos = a.sorted_pos; e.prev2 = a.prev2; e.prev3 = a.prev3;
-    e.nice = a.nice_len; e.depth = a.depth; e.hb = a.hash_bytes; e.cyclic = a.dict_size + 1;
-    e.block_end = 0; e.n_last = a.n - 1;
-    e.mlen = nullptr; e.mdist = nullptr; e.packed = a.list_packed;
-    Pre P;
-    P.valid = false; P.pos = 0; P.ent = 0;
-    P.a.rk = P.a.d2 = P.a.d3 = 0; P.an = P.a;
-    uint32_t span_end = 0;
-    for (uint32_t x = x0; x < x1; ++x) {
-        if (x >= span_end) {
-            const uint32_t blk = x / a.block_size;
-            const uint32_t block_start = blk * a.block_size;
-            const uint32_t block_end = min(a.n, block_start + a.block_size);
-            const uint64_t k = (x - block_start) / a.span_size;
-            const uint64_t se = (uint64_t)block_start + (k + 1) * a.span_size;
-            span_end = se < block_end ? (uint32_t)se : block_end;
-            e.block_end = block_end;
-        }
-        Round R;
-        do_round<false>(e, P, x, span_end, 0, 0, 0, 0, R);
-        const uint64_t lt = (1ull << lane) - 1;
-        const bool rec = (R.mask >> lane) & 1;
-        const uint32_t idx = (uint32_t)__builtin_popcountll(R.mask & lt);
-        const uint32_t cnt = (uint32_t)__builtin_popcountll(R.mask);
-        const uint32_t drop = cnt > LIST_K ? cnt - LIST_K : 0;
-        const uint64_t rec_base = (uint64_t)x * LIST_W;
-        if (rec && idx >= drop) {
-            const uint32_t len = idx + 1 == cnt ? R.longest : R.L;
-            const uint64_t o = rec_base + (idx - drop);
-            if (e.packed) {
-                mdist[o] = (len << 23) | R.D;
-            } else {
-                mlen[o] = (uint16_t)len;
-                mdist[o] = R.D;
-            }
-        }
-        if (lane == 0) mdist[rec_base + LIST_K] = cnt - drop;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// x86 BCJ encoder (simple/x86.c:26-118), one Block = one fresh filter (x86.c:121-136), start offset 0.
-// The filter is a sequential state machine, but (1) every decision reads ORIGINAL bytes only -- a
-// converted CALL/JMP skips its own four operand bytes, nothing re-reads a patched byte -- and (2) its
-// state (prev_mask, prev_pos) is void at any position preceded by five bytes without an E8/E9: the
-// next opcode then sees offset > 5 and clears prev_mask whatever came before, and no conversion can
-// straddle such a position.  So a chunk owner starts at the first such synchronisation point of its
-// chunk and runs to the first one at or after the chunk end (= where the next owner starts): exact,
-// chunk-parallel, and sequential only on input without synchronisation points.
-// `out` already holds a copy of `in`; only converted operands are written.
-// ------------------------------------------------------------------------------------------
-constexpr uint32_t BCJ_CHUNK = 2048;
-
-__device__ __forceinline__ bool x86_is_op(uint32_t b) { return (b & 0xFEu) == 0xE8u; }
-__device__ __forceinline__ bool x86_ms(uint32_t b) { return b == 0u || b == 0xFFu; }
-
-__global__ __launch_bounds__(256) void k_x86_bcj(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
-        uint32_t block_size, uint32_t chunks_per_block, uint32_t nchunks)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nchunks) return;
-    const uint32_t blk = t / chunks_per_block, k = t - blk * chunks_per_block;
-    const uint32_t bs = blk * block_size;
-    if (bs >= n) return;
-    const uint32_t size = min(n - bs, block_size);
-    if (size < 5) return;
-    const uint32_t limit = size - 5;                 // last position the filter examines
-    const uint32_t s = k * BCJ_CHUNK;
-    if (s > limit) return;
-    const uint32_t e = s + BCJ_CHUNK;                // may exceed size; only compared
-    const uint8_t* __restrict__ b = in + bs;
-    uint8_t* __restrict__ o = out + bs;
-    uint32_t pos = 0, run = 0;                       // run = non-opcode bytes immediately before pos
-    if (k != 0) {
-        bool found = false;
-        for (uint32_t q = s - 5; q <= limit && q < e; ++q) {
-            if (q >= s && run >= 5) { pos = q; found = true; break; }
-            run = x86_is_op(b[q]) ? 0u : run + 1;
-        }
-        if (!found) return;                           // the previous owner runs through this chunk
-    }
-    uint32_t prev_mask = 0, prev_pos = pos - 6;       // "long ago" (x86.c:133: -5 at the Block start acts the same)
-    while (pos <= limit) {
-        if (pos >= e && run >= 5) break;              // next owner's start
-        const uint32_t c = b[pos];
-        if (!x86_is_op(c)) { ++pos; ++run; continue; }
-        const uint32_t offset = pos - prev_pos;
-        prev_pos = pos;
-        if (offset > 5) prev_mask = 0;
-        else for (uint32_t i = 0; i < offset; ++i) prev_mask = (prev_mask & 0x77u) << 1;
-        uint32_t b4 = b[pos + 4];
-        if (x86_ms(b4) && (prev_mask >> 1) <= 4 && (prev_mask >> 1) != 3) {
-            const uint32_t b1 = b[pos + 1], b2 = b[pos + 2], b3 = b[pos + 3];
-            uint32_t src = (b4 << 24) | (b3 << 16) | (b2 << 8) | b1;
-            uint32_t dest;
-            for (;;) {
-                dest = src + (pos + 5);
-                if (prev_mask == 0) break;
-                const uint32_t pm = prev_mask >> 1;
-                const uint32_t i = pm == 0 ? 0u : pm == 1 ? 1u : pm <= 3 ? 2u : 3u;    // MASK_TO_BIT_NUMBER
-                const uint32_t bb = (dest >> (24 - i * 8)) & 0xFFu;
-                if (!x86_ms(bb)) break;
-                src = dest ^ ((1u << (32 - i * 8)) - 1);
-            }
-            o[pos + 4] = (uint8_t)(~(((dest >> 24) & 1) - 1));
-            o[pos + 3] = (uint8_t)(dest >> 16);
-            o[pos + 2] = (uint8_t)(dest >> 8);
-            o[pos + 1] = (uint8_t)dest;
-            run = x86_is_op(b1) ? 0u : 1u;
-            run = x86_is_op(b2) ? 0u : run + 1;
-            run = x86_is_op(b3) ? 0u : run + 1;
-            run = x86_is_op(b4) ? 0u : run + 1;
-            pos += 5;
-            prev_mask = 0;
-        } else {
-            ++pos;
-            run = 0;
-            prev_mask |= 1;
-            if (x86_ms(b4)) prev_mask |= 0x10;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// ARM64 BCJ encoder (simple/arm64.c:20-105) and delta encoder (delta/delta_encoder.c:20-45), one fresh
-// filter per Block, start offset 0.  Both are stateless given the ORIGINAL bytes (ARM64: every aligned
-// 4-byte instruction on its own, pc = offset inside the Block; delta: byte minus the byte `dist` before it
-// in the Block, zero history), so they are plain data-parallel maps -- one thread per instruction / byte.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_arm64_bcj(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
-        uint32_t block_size, uint32_t nblocks)
-{
-    const uint32_t spb = block_size / 4;                      // instruction slots per full Block
-    if (spb == 0) return;
-    const uint64_t total = (uint64_t)spb * nblocks;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const uint32_t b = (uint32_t)(t / spb), k = (uint32_t)(t - (uint64_t)b * spb);
-        const uint32_t bs = b * block_size;
-        if (bs >= n) continue;
-        const uint32_t len = min(n - bs, block_size) & ~3u;   // arm64.c:26: the tail (size & 3) stays as it is
-        const uint32_t pc = k * 4;
-        if (pc + 4 > len) continue;
-        const uint32_t g = bs + pc;
-        uint32_t instr;
-        __builtin_memcpy(&instr, in + g, 4);
-        if ((instr >> 26) == 0x25) {
-            instr = 0x94000000u | ((instr + (pc >> 2)) & 0x03FFFFFFu);
-            __builtin_memcpy(out + g, &instr, 4);
-        } else if ((instr & 0x9F000000u) == 0x90000000u) {
-            const uint32_t src = ((instr >> 29) & 3) | ((instr >> 3) & 0x001FFFFCu);
-            if ((src + 0x00020000u) & 0x001C0000u) continue;
-            instr &= 0x9000001Fu;
-            const uint32_t dest = src + (pc >> 12);
-            instr |= (dest & 3) << 29;
-            instr |= (dest & 0x0003FFFCu) << 3;
-            instr |= (0u - (dest & 0x00020000u)) & 0x00E00000u;
-            __builtin_memcpy(out + g, &instr, 4);
-        }
-    }
-}
-
-// ARM / PowerPC / SPARC (simple/arm.c, powerpc.c, sparc.c: one 4-byte instruction per slot), ARM-Thumb
-// (simple/armthumb.c: 2-byte slots, a BL pair is 4 bytes) and IA-64 (simple/ia64.c: 16-byte bundles of three
-// 41-bit slots).  pc = offset inside the Block (start offset 0); the tail the reference leaves unfiltered
-// (size & 3, size & 15, the last < 4 bytes) stays as it is.  Every slot converts on its own: in ARM-Thumb the
-// reference skips the halfword behind a converted pair, but that halfword can never start a pair itself (its
-// second byte would have to be 0xF0..0xF7 and 0xF8..0xFF at once), so the slots are independent there too.
-__global__ __launch_bounds__(256) void k_bcj_simple(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
-        uint32_t block_size, uint32_t nblocks, uint32_t kind)
-{
-    const uint32_t unit = kind == 8 ? 2u : kind == 6 ? 16u : 4u;
-    const uint32_t spb = block_size / unit;                   // slots per full Block
-    if (spb == 0) return;
-    const uint64_t total = (uint64_t)spb * nblocks;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const uint32_t b = (uint32_t)(t / spb), k = (uint32_t)(t - (uint64_t)b * spb);
-        const uint32_t bs = b * block_size;
-        if (bs >= n) continue;
-        const uint32_t blen = min(n - bs, block_size);
-        const uint32_t pc = k * unit;
-        const uint8_t* p = in + bs + pc;
-        uint8_t* q = out + bs + pc;
-        if (kind == 8) {                                      // ARM-Thumb BL pair
-            if (blen < 4 || pc > blen - 4) continue;
-            if ((p[1] & 0xF8u) != 0xF0u || (p[3] & 0xF8u) != 0xF8u) continue;
-            uint32_t src = ((uint32_t)(p[1] & 7u) << 19) | ((uint32_t)p[0] << 11) | ((uint32_t)(p[3] & 7u) << 8) | p[2];
-            src <<= 1;
-            const uint32_t dest = (pc + 4 + src) >> 1;
-            q[1] = (uint8_t)(0xF0u | ((dest >> 19) & 7u));
-            q[0] = (uint8_t)(dest >> 11);
-            q[3] = (uint8_t)(0xF8u | ((dest >> 8) & 7u));
-            q[2] = (uint8_t)dest;
-        } else if (kind == 6) {                               // IA-64 bundle
-            if (pc + 16 > (blen & ~15u)) continue;
-            uint8_t bun[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) bun[i] = p[i];
-            const uint32_t tmpl = bun[0] & 0x1Fu;
-            // branch slots by template (ia64.c BRANCH_TABLE): 16,17: 4  18,19: 6  22,23: 7  24,25,28,29: 4
-            const uint32_t mask = (tmpl == 16 || tmpl == 17 || tmpl == 24 || tmpl == 25 || tmpl == 28 || tmpl == 29) ? 4u
-                    : (tmpl == 18 || tmpl == 19) ? 6u : (tmpl == 22 || tmpl == 23) ? 7u : 0u;
-            bool changed = false;
-            uint32_t bit_pos = 5;
-            for (uint32_t slot = 0; slot < 3; ++slot, bit_pos += 41) {
-                if (((mask >> slot) & 1u) == 0) continue;
-                const uint32_t byte_pos = bit_pos >> 3, bit_res = bit_pos & 7u;
-                uint64_t instruction = 0;
-                for (uint32_t j = 0; j < 6; ++j) instruction += (uint64_t)bun[j + byte_pos] << (8 * j);
-                uint64_t norm = instruction >> bit_res;
-                if (((norm >> 37) & 0xFu) != 0x5u || ((norm >> 9) & 0x7u) != 0) continue;
-                uint32_t src = (uint32_t)((norm >> 13) & 0xFFFFFu);
-                src |= (uint32_t)((norm >> 36) & 1u) << 20;
-                src <<= 4;
-                const uint32_t dest = (pc + src) >> 4;
-                norm &= ~((uint64_t)0x8FFFFF << 13);
-                norm |= (uint64_t)(dest & 0xFFFFFu) << 13;
-                norm |= (uint64_t)(dest & 0x100000u) << (36 - 20);
-                instruction &= (1u << bit_res) - 1;
-                instruction |= norm << bit_res;
-                for (uint32_t j = 0; j < 6; ++j) bun[j + byte_pos] = (uint8_t)(instruction >> (8 * j));
-                changed = true;
-            }
-            if (changed) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) q[i] = bun[i];
-            }
-        } else {
-            if (pc + 4 > (blen & ~3u)) continue;
-            if (kind == 7) {                                  // ARM BL (little endian, condition "always")
-                if (p[3] != 0xEBu) continue;
-                uint32_t src = ((uint32_t)p[2] << 16) | ((uint32_t)p[1] << 8) | p[0];
-                src <<= 2;
-                const uint32_t dest = (pc + 8 + src) >> 2;
-                q[2] = (uint8_t)(dest >> 16); q[1] = (uint8_t)(dest >> 8); q[0] = (uint8_t)dest;
-            } else if (kind == 5) {                           // PowerPC b/bl with AA = 0, LK = 1 (big endian)
-                if ((p[0] >> 2) != 0x12u || (p[3] & 3u) != 1u) continue;
-                const uint32_t src = ((uint32_t)(p[0] & 3u) << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (p[3] & ~3u);
-                const uint32_t dest = pc + src;
-                q[0] = (uint8_t)(0x48u | ((dest >> 24) & 3u));
-                q[1] = (uint8_t)(dest >> 16);
-                q[2] = (uint8_t)(dest >> 8);
-                q[3] = (uint8_t)((p[3] & 3u) | (dest & 0xFFu));
-            } else {                                          // SPARC call (big endian)
-                if (!((p[0] == 0x40u && (p[1] & 0xC0u) == 0x00u) || (p[0] == 0x7Fu && (p[1] & 0xC0u) == 0xC0u))) continue;
-                uint32_t src = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-                src <<= 2;
-                uint32_t dest = (pc + src) >> 2;
-                dest = (((0u - ((dest >> 22) & 1u)) << 22) & 0x3FFFFFFFu) | (dest & 0x3FFFFFu) | 0x40000000u;
-                q[0] = (uint8_t)(dest >> 24); q[1] = (uint8_t)(dest >> 16); q[2] = (uint8_t)(dest >> 8); q[3] = (uint8_t)dest;
-            }
-        }
-    }
-}
-
-// RISC-V (simple/riscv.c:352-609, encoder).  The reference walks the Block in 2-byte steps; what it finds at an
-// examined position decides how far it jumps: 2 (nothing), 4 (a converted JAL, or an AUIPC with rd x0/x2 that is
-// not the special form), 6 (an AUIPC that has no partner), 8 (a converted AUIPC pair in either direction).  All
-// of that is read from bytes no earlier conversion has touched, so step(i) is a function of the input, and a
-// position is examined unless an examined position 2, 4 or 6 bytes before it jumps over it.  Hence the
-// synchronisation rule used to cut the walk into chunks (the x86 kernel above does the same with its own
-// rule): a position whose three predecessors cannot reach over it whatever their state -- step(i-2) <= 2,
-// step(i-4) <= 4, step(i-6) <= 6 -- is examined by every walk.  Each chunk's owner starts at the first such
-// position inside its chunk and stops at the first one behind its chunk.
-__device__ __forceinline__ uint32_t rv_rd32(const uint8_t* p)
-{
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-// not a pair: rd of the AUIPC != rs1 of the second instruction, or its two lowest opcode bits are not 11
-__device__ __forceinline__ bool rv_not_pair(uint32_t auipc, uint32_t inst2) { return (((auipc << 8) ^ inst2) & 0xF8003u) != 3u; }
-// the special form the encoder itself produces: rd = x2, bits 13:12 = 11, and a "rs1" that is neither x0 nor x2
-__device__ __forceinline__ bool rv_special(uint32_t auipc) { return (auipc & 0x3FFFu) == 0x3117u && ((auipc >> 27) & 0x1Du) != 0; }
-__device__ __forceinline__ uint32_t rv_step(const uint8_t* b, uint32_t i, uint32_t limit)
-{
-    if (i > limit) return 2;
-    const uint32_t b0 = b[i];
-    if (b0 == 0xEFu) return (b[i + 1] & 0x0Du) ? 2u : 4u;
-    if ((b0 & 0x7Fu) != 0x17u) return 2;
-    const uint32_t inst = rv_rd32(b + i);
-    if (inst & 0xE80u) return rv_not_pair(inst, rv_rd32(b + i + 4)) ? 6u : 8u;
-    return rv_special(inst) ? 8u : 4u;
-}
-__device__ __forceinline__ bool rv_sync(const uint8_t* b, uint32_t i, uint32_t limit)
-{
-    return (i < 2 || rv_step(b, i - 2, limit) <= 2) && (i < 4 || rv_step(b, i - 4, limit) <= 4) && (i < 6 || rv_step(b, i - 6, limit) <= 6);
-}
-
-__global__ __launch_bounds__(256) void k_riscv_bcj(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
-        uint32_t block_size, uint32_t chunks_per_block, uint32_t nchunks)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nchunks) return;
-    const uint32_t blk = t / chunks_per_block, k = t - blk * chunks_per_block;
-    const uint32_t bs = blk * block_size;
-    if (bs >= n) return;
-    const uint32_t size = min(n - bs, block_size);
-    if (size < 8) return;
-    const uint32_t limit = size - 8;                 // last position the filter examines (riscv.c:364-372)
-    const uint32_t s = k * BCJ_CHUNK;                // BCJ_CHUNK is even
-    if (s > limit) return;
-    const uint32_t e = s + BCJ_CHUNK;
-    const uint8_t* __restrict__ b = in + bs;
-    uint8_t* __restrict__ o = out + bs;
-    uint32_t pos = 0;
-    if (k != 0) {
-        bool found = false;
-        for (uint32_t q = s; q <= limit && q < e; q += 2)
-            if (rv_sync(b, q, limit)) { pos = q; found = true; break; }
-        if (!found) return;                          // the previous owner walks through this chunk
-    }
-    while (pos <= limit) {
-        if (pos >= e && rv_sync(b, pos, limit)) break;      // the next owner's start
-        const uint32_t b0 = b[pos];
-        if (b0 == 0xEFu) {
-            // JAL with rd = x1 / x5: pc-relative 20-bit immediate -> absolute, stored big endian (riscv.c:379-438)
-            const uint32_t b1 = b[pos + 1];
-            if (b1 & 0x0Du) { pos += 2; continue; }
-            const uint32_t b2 = b[pos + 2], b3 = b[pos + 3];
-            uint32_t addr = ((b1 & 0xF0u) << 8) | ((b2 & 0x0Fu) << 16) | ((b2 & 0x10u) << 7) | ((b2 & 0xE0u) >> 4)
-                    | ((b3 & 0x7Fu) << 4) | ((b3 & 0x80u) << 13);
-            addr += pos;
-            o[pos + 1] = (uint8_t)((b1 & 0x0Fu) | ((addr >> 13) & 0xF0u));
-            o[pos + 2] = (uint8_t)(addr >> 9);
-            o[pos + 3] = (uint8_t)(addr >> 1);
-            pos += 4;
-        } else if ((b0 & 0x7Fu) == 0x17u) {
-            uint32_t inst = rv_rd32(b + pos);
-            if (inst & 0xE80u) {
-                // AUIPC with rd other than x0 / x2 (riscv.c:440-551)
-                const uint32_t inst2 = rv_rd32(b + pos + 4);
-                if (rv_not_pair(inst, inst2)) { pos += 6; continue; }
-                uint32_t addr = inst & 0xFFFFF000u;
-                addr += (inst2 >> 20) - ((inst2 >> 19) & 0x1000u);
-                addr += pos;
-                inst = 0x17u | (2u << 7) | (inst2 << 12);
-                o[pos] = (uint8_t)inst; o[pos + 1] = (uint8_t)(inst >> 8); o[pos + 2] = (uint8_t)(inst >> 16); o[pos + 3] = (uint8_t)(inst >> 24);
-                o[pos + 4] = (uint8_t)(addr >> 24); o[pos + 5] = (uint8_t)(addr >> 16); o[pos + 6] = (uint8_t)(addr >> 8); o[pos + 7] = (uint8_t)addr;
-            } else {
-                // AUIPC with rd x0 / x2: only the special form is (un)converted (riscv.c:552-602)
-                if (!rv_special(inst)) { pos += 4; continue; }
-                const uint32_t fake_rs1 = inst >> 27;
-                const uint32_t fake_addr = rv_rd32(b + pos + 4);
-                const uint32_t fake_inst2 = (inst >> 12) | (fake_addr << 20);
-                inst = 0x17u | (fake_rs1 << 7) | (fake_addr & 0xFFFFF000u);
-                o[pos] = (uint8_t)inst; o[pos + 1] = (uint8_t)(inst >> 8); o[pos + 2] = (uint8_t)(inst >> 16); o[pos + 3] = (uint8_t)(inst >> 24);
-                o[pos + 4] = (uint8_t)fake_inst2; o[pos + 5] = (uint8_t)(fake_inst2 >> 8); o[pos + 6] = (uint8_t)(fake_inst2 >> 16);
-                o[pos + 7] = (uint8_t)(fake_inst2 >> 24);
-            }
-            pos += 8;
-        } else {
-            pos += 2;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_delta(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
-        uint32_t block_size, uint32_t dist)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += stride) {
-        const uint32_t bs = (g / block_size) * block_size;
-        const uint8_t prev = g - bs >= dist ? in[g - dist] : (uint8_t)0;
-        out[g] = (uint8_t)(in[g] - prev);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// SHA-256 Block check (check/sha256.c:120-189, FIPS 180-4): a serial hash per Block, so one THREAD per
-// Block (Blocks are the parallelism; the default Check, CRC64, stays the fast path).  32 bytes per Block.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rotr32(uint32_t x, uint32_t r) { return (x >> r) | (x << (32 - r)); }
-
-__global__ __launch_bounds__(64) void k_sha256_blocks(const uint8_t* __restrict__ in, uint32_t n, uint32_t block_size,
-        uint32_t nblocks, uint8_t* __restrict__ out)
-{
-    static const uint32_t K[64] = {
-        0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01,
-        0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc,
-        0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147,
-        0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-        0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08,
-        0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208,
-        0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2 };
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nblocks) return;
-    const uint32_t bs = b * block_size;
-    const uint32_t len = min(n, bs + block_size) - bs;
-    uint32_t h[8] = { 0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19 };
-    const uint32_t nchunks = (len + 9 + 63) / 64;               // message + 0x80 + 64-bit length
-    const uint32_t nfull = len / 64;                            // chunks that are message bytes only
-    // A SHA-256 is one serial chain of 64-byte compressions, so the parallelism is the Blocks: one LANE per Block (a
-    // wavefront hashes 64 Blocks in lockstep).  Message words come in 16-byte loads, the schedule lives in a 16-word
-    // ring in registers, the 64 rounds are unrolled.
-    for (uint32_t c = 0; c < nchunks; ++c) {
-        uint32_t w[16];
-        if (c < nfull) {
-            const uint8_t* p = in + bs + (uint64_t)c * 64;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint4 v;
-                __builtin_memcpy(&v, p + 16 * q, 16);
-                w[4 * q + 0] = __builtin_bswap32(v.x); w[4 * q + 1] = __builtin_bswap32(v.y);
-                w[4 * q + 2] = __builtin_bswap32(v.z); w[4 * q + 3] = __builtin_bswap32(v.w);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                uint32_t v = 0;
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t o = c * 64 + i * 4 + k;
-                    uint32_t byte = 0;
-                    if (o < len) byte = in[bs + o];
-                    else if (o == len) byte = 0x80;
-                    else if (c + 1 == nchunks && i >= 14) {
-                        const uint64_t bits = (uint64_t)len * 8;
-                        byte = (uint32_t)(bits >> (8 * (7 - ((i - 14) * 4 + k)))) & 0xFF;
-                    }
-                    v = (v << 8) | byte;
-                }
-                w[i] = v;
-            }
-        }
-        uint32_t a = h[0], bb = h[1], cc = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-#pragma unroll
-        for (int i = 0; i < 64; ++i) {
-            if (i >= 16) {
-                const uint32_t w15 = w[(i - 15) & 15], w2 = w[(i - 2) & 15];
-                const uint32_t s0 = rotr32(w15, 7) ^ rotr32(w15, 18) ^ (w15 >> 3);
-                const uint32_t s1 = rotr32(w2, 17) ^ rotr32(w2, 19) ^ (w2 >> 10);
-                w[i & 15] = w[i & 15] + s0 + w[(i - 7) & 15] + s1;
-            }
-            const uint32_t S1 = rotr32(e, 6) ^ rotr32(e, 11) ^ rotr32(e, 25);
-            const uint32_t ch = (e & f) ^ (~e & g);
-            const uint32_t t1 = hh + S1 + ch + K[i] + w[i & 15];
-            const uint32_t S0 = rotr32(a, 2) ^ rotr32(a, 13) ^ rotr32(a, 22);
-            const uint32_t mj = (a & bb) ^ (a & cc) ^ (bb & cc);
-            const uint32_t t2 = S0 + mj;
-            hh = g; g = f; f = e; e = d + t1; d = cc; cc = bb; bb = a; a = t1 + t2;
-        }
-        h[0] += a; h[1] += bb; h[2] += cc; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
-    }
-    for (int i = 0; i < 8; ++i) {
-        out[b * 32 + i * 4 + 0] = (uint8_t)(h[i] >> 24);
-        out[b * 32 + i * 4 + 1] = (uint8_t)(h[i] >> 16);
-        out[b * 32 + i * 4 + 2] = (uint8_t)(h[i] >> 8);
-        out[b * 32 + i * 4 + 3] = (uint8_t)h[i];
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// CRC64 (check/crc64_fast.c; ECMA-182 reflected, poly 0xC96C5795D7870F42)
-// ------------------------------------------------------------------------------------------
-// Both Block checks of the device path share the code: T = uint64_t is CRC64 (ECMA-182 reflected,
-// check/crc64_fast.c), T = uint32_t is CRC32 (IEEE reflected, check/crc32_fast.c).
-template <typename T> struct CrcP;
-template <> struct CrcP<uint64_t> { static constexpr uint64_t POLY = 0xC96C5795D7870F42ull; static constexpr uint64_t TOP = 1ull << 63; };
-template <> struct CrcP<uint32_t> { static constexpr uint32_t POLY = 0xEDB88320u; static constexpr uint32_t TOP = 1u << 31; };
-
-// product of two residues in the reflected representation (MSB = x^0)
-template <typename T>
-__device__ __forceinline__ T gf_mul(T a, T b)
-{
-    T r = 0;
-    for (int i = 0; i < (int)(8 * sizeof(T)); ++i) {
-        if (a & CrcP<T>::TOP) r ^= b;
-        a <<= 1;
-        b = (T)((b >> 1) ^ ((b & 1) ? CrcP<T>::POLY : (T)0));
-    }
-    return r;
-}
-
-template <typename T>
-__device__ __forceinline__ T gf_xpow8(uint64_t nbytes)
-{
-    T base = (T)(CrcP<T>::TOP >> 8);     // x^8
-    T acc = CrcP<T>::TOP;                // 1
-    while (nbytes) {
-        if (nbytes & 1) acc = gf_mul<T>(acc, base);
-        base = gf_mul<T>(base, base);
-        nbytes >>= 1;
-    }
-    return acc;
-}
-
-// Standard CRC (init ~0, final ~) of each strip of `strip` bytes; strips never straddle Blocks.
-template <typename T>
-__global__ __launch_bounds__(256) void k_crc_strips(const uint8_t* __restrict__ in, uint32_t n,
-        uint32_t block_size, uint32_t strip, uint32_t strips_per_block, uint32_t nstrips,
-        T* __restrict__ out)
-{
-    __shared__ T tab[256];
-    {
-        T r = (T)threadIdx.x;
-        for (int k = 0; k < 8; ++k) r = (T)((r >> 1) ^ ((r & 1) ? CrcP<T>::POLY : (T)0));
-        tab[threadIdx.x] = r;
-    }
-    __syncthreads();
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nstrips) return;
-    const uint32_t b = s / strips_per_block;
-    const uint32_t bstart = b * block_size;
-    const uint32_t bend = min(n, bstart + block_size);
-    const uint32_t beg = bstart + (s - b * strips_per_block) * strip;
-    T crc = (T)~(T)0;
-    if (beg < bend) {
-        const uint32_t end = min(bend, beg + strip);
-        for (uint32_t i = beg; i < end; ++i)
-            crc = (T)(tab[(crc ^ in[i]) & 0xFF] ^ (crc >> 8));
-    }
-    out[s] = (T)~crc;
-}
-
-// One wave per Block: fold the strip CRCs left to right: crc(A||B) = crc(A)*x^(8|B|) ^ crc(B).
-// The Block's check is written as a uint64_t (CRC32 zero-extended).
-template <typename T>
-__global__ __launch_bounds__(64) void k_crc_fold(const T* __restrict__ strips, uint32_t n,
-        uint32_t block_size, uint32_t strip, uint32_t strips_per_block, uint64_t* __restrict__ block_crc)
-{
-    const uint32_t b = blockIdx.x;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t bstart = b * block_size;
-    const uint32_t bend = min(n, bstart + block_size);
-    const uint32_t blen = bend - bstart;
-    const uint32_t ns = (blen + strip - 1) / strip;          // strips actually used
-    const uint32_t per = (ns + 63) / 64;
-    const uint32_t s0 = min(ns, lane * per), s1 = min(ns, s0 + per);
-    const T xs = gf_xpow8<T>(strip);
-    // lane-local fold over its contiguous strips
-    T acc = 0;              // crc of the empty string is 0 and is the identity of the fold
-    uint64_t bytes = 0;
-    for (uint32_t s = s0; s < s1; ++s) {
-        const uint32_t len = min(strip, blen - s * strip);
-        const T c = strips[(uint64_t)b * strips_per_block + s];
-        acc = (T)(gf_mul<T>(acc, len == strip ? xs : gf_xpow8<T>(len)) ^ c);
-        bytes += len;
-    }
-    // sequential combine across lanes (64 steps, once per Block)
-    T total = 0;
-    for (uint32_t l = 0; l < 64; ++l) {
-        const T cl = (T)__shfl((unsigned long long)acc, l);
-        const uint64_t bl = __shfl((unsigned long long)bytes, l);
-        if (bl) total = (T)(gf_mul<T>(total, gf_xpow8<T>(bl)) ^ cl);
-    }
-    if (lane == 0) block_crc[b] = (uint64_t)total;
-}
-
-// ------------------------------------------------------------------------------------------
 // Assembly: gather span outputs (and small literal pieces prepared by the host: headers,
 // end markers, padding, checks, index, footer) into the final stream buffer.
 // One workgroup per copy segment.
-// out[key[i]] = v[i] for a permutation `key` of 0..n-1: radix passes over the key bits above INV_LOW, then the LDS
-// step.  keys_cur / vals_cur hold the pairs, the *_alt buffers are scratch; all four are clobbered.
-// u32 values: out may be one of the value buffers.  u64 values: out_lo / out_hi must not overlap them.
-template <typename V>
-static hipError_t invert_perm(uint32_t* keys_cur, uint32_t* keys_alt, V* vals_cur, V* vals_alt, uint32_t n,
-        uint32_t* out_lo, uint32_t* out_hi, void* tmp, size_t tmp_bytes, hipStream_t st)
-{
-    if (n == 0) return hipSuccess;
-    uint32_t bits = 1;
-    while (bits < 32 && (1ull << bits) < n) ++bits;
-    rocprim::double_buffer<uint32_t> kb(keys_cur, keys_alt);
-    rocprim::double_buffer<V> vb(vals_cur, vals_alt);
-    if (bits > INV_LOW) {
-        size_t need = 0;
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, need, kb, vb, (size_t)n, INV_LOW, bits, st);
-        if (e != hipSuccess) return e;
-        if (need > tmp_bytes) return hipErrorOutOfMemory;
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)n, INV_LOW, bits, st);
-        if (e != hipSuccess) return e;
-    }
-    const uint32_t nb = (n + (1u << INV_LOW) - 1) >> INV_LOW;
-    if constexpr (sizeof(V) == 4)
-        hipLaunchKernelGGL(k_inv_low_u32, dim3(nb), dim3(1024), 0, st, kb.current(),
-                reinterpret_cast<const uint32_t*>(vb.current()), n, out_lo);
-    else
-        hipLaunchKernelGGL(k_inv_low_u64, dim3(nb), dim3(1024), 0, st, kb.current(),
-                reinterpret_cast<const uint64_t*>(vb.current()), n, out_lo, out_hi);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_assemble(const xzamd_copy_seg* __restrict__ segs, uint32_t nsegs,
         const uint8_t* __restrict__ scratch, const uint8_t* __restrict__ lits, const uint8_t* __restrict__ in,
@@ -4468,387 +2657,12 @@ __global__ __launch_bounds__(256) void k_assemble(const xzamd_copy_seg* __restri
     }
 }
 
-inline uint32_t grid_for(uint64_t n, uint32_t threads, uint32_t cap)
-{
-    uint64_t g = (n + threads - 1) / threads;
-    if (g > cap) g = cap;
-    if (g == 0) g = 1;
-    return (uint32_t)g;
-}
-
 } // namespace
 
 // ==========================================================================================
 // extern "C" launch wrappers (internal ABI between the plain-C host layer and the kernels)
 // ==========================================================================================
 extern "C" {
-
-int xzk_sort_temp_bytes(uint32_t n, uint32_t end_bit, uint64_t* bytes)
-{
-    size_t sz = 0;
-    rocprim::double_buffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, sz, k, v, (size_t)n, 0u, end_bit, (hipStream_t)0);
-    *bytes = sz;
-    return (int)e;
-}
-
-// temporary storage the suffix-order build needs (largest of its three primitives)
-int xzk_sa_temp_bytes(uint32_t n, uint64_t* bytes)
-{
-    size_t best = 0, sz = 0;
-    {
-        rocprim::double_buffer<uint64_t> k(nullptr, nullptr);
-        rocprim::double_buffer<uint32_t> v(nullptr, nullptr);
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, sz, k, v, (size_t)n, 0u, 64u, (hipStream_t)0);
-        if (e != hipSuccess) return (int)e;
-        best = sz > best ? sz : best;
-    }
-    {
-        rocprim::double_buffer<uint32_t> k(nullptr, nullptr);
-        rocprim::double_buffer<uint64_t> v(nullptr, nullptr);
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, sz, k, v, (size_t)n, 0u, 32u, (hipStream_t)0);
-        if (e != hipSuccess) return (int)e;
-        best = sz > best ? sz : best;
-    }
-    {
-        hipError_t e = rocprim::inclusive_scan(nullptr, sz, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n,
-                rocprim::maximum<uint32_t>(), (hipStream_t)0);
-        if (e != hipSuccess) return (int)e;
-        best = sz > best ? sz : best;
-    }
-    *bytes = best;
-    return 0;
-}
-
-// Builds the match-finder structure of a batch.
-//   exact finder (sa == NULL):   rank / sorted_pos (main chain), prev2, prev3
-//   suffix-neighbourhood finder: prev2, prev4, the suffix order sa / sa_rank and its by-products
-//                                rp8 / rp16: per position (rank of the round, distance to the nearest earlier
-//                                position with the same 8 / 16 bytes)
-// keys_a/keys_b/vals_a/vals_b: n u32 each; key64_a/key64_b: n u64 each (sa != NULL only).
-int xzk_build_chains(const uint8_t* d_in, uint32_t n, uint32_t block_size, uint32_t nblocks,
-        uint32_t hash_bytes, uint32_t hash_mask, uint32_t hash_bits, uint32_t sa_depth,
-        uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
-        void* sort_tmp, uint64_t sort_tmp_bytes,
-        uint32_t* rank, uint32_t* sorted_pos, uint32_t* prev2, uint32_t* prev3,
-        uint32_t* prev4, uint64_t* rp8, uint64_t* rp16, uint64_t* key64_a, uint64_t* key64_b,
-        uint32_t* sa, uint32_t* sa_rank, uint32_t* prev24, uint32_t* prev32, void* stream_)
-{
-    hipStream_t st = (hipStream_t)stream_;
-    const uint32_t g = grid_for(n, 256, 256 * 16);
-    uint32_t bb = 0;
-    while ((1u << bb) < nblocks + 1) ++bb;
-    size_t tb = sort_tmp_bytes;
-    const uint32_t which_list[3] = { 2u, 3u, 0u };
-    // hash2 heads without a sort when the segment tables fit the scratch (always, except for tiny Blocks)
-    const uint32_t h2_spb = (block_size + H2_SEG - 1) / H2_SEG;
-    const bool h2_direct = hash_bytes >= 2 && nblocks != 0 && (uint64_t)nblocks * h2_spb * 1024ull <= (uint64_t)n;
-    if (h2_direct) {
-        const uint32_t nseg = nblocks * h2_spb;
-        hipLaunchKernelGGL(k_h2_last, dim3(nseg), dim3(64), 0, st, d_in, n, block_size, h2_spb, hash_bytes, keys_a);
-        hipLaunchKernelGGL(k_h2_scan, dim3(nblocks * 4), dim3(256), 0, st, keys_a, h2_spb);
-        hipLaunchKernelGGL(k_h2_prev, dim3(nseg), dim3(64), 0, st, d_in, n, block_size, h2_spb, hash_bytes, keys_a, prev2);
-    }
-    for (int w = 0; w < 3; ++w) {
-        const uint32_t which = which_list[w];
-        if (which == 2 && h2_direct) continue;
-        if (which == 3 && (hash_bytes != 4 || sa != nullptr)) continue;      // the suffix-neighbourhood finder has no hash3 head
-        const uint32_t kbits = which == 2 ? 10u : (which == 3 ? 16u : hash_bits);
-        hipLaunchKernelGGL(k_hash_keys, dim3(g), dim3(256), 0, st, d_in, n, block_size, nblocks, hash_bytes,
-                hash_mask, hash_bits, which, keys_a, vals_a);
-        rocprim::double_buffer<uint32_t> kb(keys_a, keys_b);
-        rocprim::double_buffer<uint32_t> vb(vals_a, vals_b);
-        size_t need = 0;
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, need, kb, vb, (size_t)n, 0u, kbits + bb, st);
-        if (e != hipSuccess) return (int)e;
-        if (need > tb) return (int)hipErrorOutOfMemory;
-        e = rocprim::radix_sort_pairs(sort_tmp, tb, kb, vb, (size_t)n, 0u, kbits + bb, st);
-        if (e != hipSuccess) return (int)e;
-        uint32_t* const target = which == 2 ? prev2 : which == 3 ? prev3 : sa != nullptr ? prev4 : nullptr;
-        if (target != nullptr) {
-            // distances in sorted order, then back to position order by a sort on the position
-            hipLaunchKernelGGL(k_link_prev_seq, dim3(g), dim3(256), 0, st, kb.current(), vb.current(), n, target);
-            e = invert_perm<uint32_t>(vb.current(), vb.alternate(), target, kb.current(), n, target, nullptr, sort_tmp, tb, st);
-            if (e != hipSuccess) return (int)e;
-        } else {
-            hipLaunchKernelGGL(k_link_main, dim3(g), dim3(256), 0, st, kb.current(), vb.current(), n, sorted_pos, rank);
-        }
-    }
-    if (sa == nullptr) return (int)hipGetLastError();
-
-    // ---- suffix order ----
-    if (prev24 != nullptr && hipMemsetAsync(prev24, 0, (size_t)n * 4, st) != hipSuccess) return (int)hipErrorUnknown;
-    if (prev32 != nullptr && hipMemsetAsync(prev32, 0, (size_t)n * 4, st) != hipSuccess) return (int)hipErrorUnknown;
-    uint32_t* grp = keys_a;                       // group-start scan buffer (the hash sorts above are done with it)
-    hipError_t e;
-    size_t need = 0;
-    // round 0: chunk sort
-    hipLaunchKernelGGL(k_sa_chunk_keys, dim3(g), dim3(256), 0, st, d_in, n, block_size, key64_a, vals_a);
-    uint32_t* pos;
-    uint32_t* pos_alt;
-    if (nblocks > 1 && nblocks <= 256) {
-        // Few, large Blocks (the normal case): one sort per Block.  The positions start out in Block order, so a
-        // sort that never mixes Blocks needs no sort by Block number afterwards, and no rocprim call exceeds the
-        // 2^30 elements above which it splits every pass into two launches.
-        int in_alt = -1;
-        for (uint32_t b = 0; b < nblocks; ++b) {
-            const size_t off = (size_t)b * block_size;
-            if (off >= n) break;
-            const size_t cnt = (size_t)n - off < block_size ? (size_t)n - off : block_size;
-            rocprim::double_buffer<uint64_t> k(key64_a + off, key64_b + off);
-            rocprim::double_buffer<uint32_t> v(vals_a + off, vals_b + off);
-            e = rocprim::radix_sort_pairs(nullptr, need, k, v, cnt, 0u, 64u, st);
-            if (e != hipSuccess) return (int)e;
-            if (need > tb) return (int)hipErrorOutOfMemory;
-            e = rocprim::radix_sort_pairs(sort_tmp, tb, k, v, cnt, 0u, 64u, st);
-            if (e != hipSuccess) return (int)e;
-            const int alt = k.current() == key64_b + off;
-            if (in_alt < 0) in_alt = alt;
-            else if (alt != in_alt) {
-                // a Block of another size class took another route through rocprim: bring it to the common side
-                e = hipMemcpyAsync((in_alt ? key64_b : key64_a) + off, k.current(), cnt * 8, hipMemcpyDeviceToDevice, st);
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync((in_alt ? vals_b : vals_a) + off, v.current(), cnt * 4, hipMemcpyDeviceToDevice, st);
-                if (e != hipSuccess) return (int)e;
-            }
-        }
-        pos = in_alt ? vals_b : vals_a;
-        pos_alt = in_alt ? vals_a : vals_b;
-        hipLaunchKernelGGL(k_sa_flags64, dim3(g), dim3(256), 0, st, in_alt ? key64_b : key64_a, n, block_size, grp);
-        e = rocprim::inclusive_scan(nullptr, need, grp, grp, (size_t)n, rocprim::maximum<uint32_t>(), st);
-        if (e != hipSuccess) return (int)e;
-        if (need > tb) return (int)hipErrorOutOfMemory;
-        e = rocprim::inclusive_scan(sort_tmp, tb, grp, grp, (size_t)n, rocprim::maximum<uint32_t>(), st);
-        if (e != hipSuccess) return (int)e;
-    } else {
-        rocprim::double_buffer<uint64_t> k64(key64_a, key64_b);
-        rocprim::double_buffer<uint32_t> pv(vals_a, vals_b);
-        e = rocprim::radix_sort_pairs(nullptr, need, k64, pv, (size_t)n, 0u, 64u, st);
-        if (e != hipSuccess) return (int)e;
-        if (need > tb) return (int)hipErrorOutOfMemory;
-        e = rocprim::radix_sort_pairs(sort_tmp, tb, k64, pv, (size_t)n, 0u, 64u, st);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k_sa_flags64, dim3(g), dim3(256), 0, st, k64.current(), n, 0u, grp);
-        e = rocprim::inclusive_scan(nullptr, need, grp, grp, (size_t)n, rocprim::maximum<uint32_t>(), st);
-        if (e != hipSuccess) return (int)e;
-        if (need > tb) return (int)hipErrorOutOfMemory;
-        e = rocprim::inclusive_scan(sort_tmp, tb, grp, grp, (size_t)n, rocprim::maximum<uint32_t>(), st);
-        if (e != hipSuccess) return (int)e;
-        pos = pv.current();
-        pos_alt = pv.alternate();
-        if (nblocks > 1) {
-            // many small Blocks: one sort of everything, then a stable sort by Block number; values = (position,
-            // chunk group), the chunk keys are dead now
-            uint32_t* bk_a = keys_b;
-            uint32_t* bk_b = pos_alt;
-            uint64_t* bv_a = k64.alternate();
-            uint64_t* bv_b = k64.current();
-            hipLaunchKernelGGL(k_sa_block_keys, dim3(g), dim3(256), 0, st, pos, grp, n, block_size, bk_a, bv_a);
-            rocprim::double_buffer<uint32_t> bk(bk_a, bk_b);
-            rocprim::double_buffer<uint64_t> bv(bv_a, bv_b);
-            e = rocprim::radix_sort_pairs(nullptr, need, bk, bv, (size_t)n, 0u, bb, st);
-            if (e != hipSuccess) return (int)e;
-            if (need > tb) return (int)hipErrorOutOfMemory;
-            e = rocprim::radix_sort_pairs(sort_tmp, tb, bk, bv, (size_t)n, 0u, bb, st);
-            if (e != hipSuccess) return (int)e;
-            // positions go back to `pos` (vals buffer that held them before; its content is dead)
-            hipLaunchKernelGGL(k_sa_block_unpack, dim3(g), dim3(256), 0, st, bk.current(), bv.current(), n, pos, grp);
-            // pos_alt may have been used as a key buffer: both vals buffers are free for reuse below except `pos`
-            e = rocprim::inclusive_scan(sort_tmp, tb, grp, grp, (size_t)n, rocprim::maximum<uint32_t>(), st);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-    // doubling rounds
-    uint32_t sbits = 1, fbits = 1;                    // bits of a Block-relative rank (<= block_size), of a rank (<= n)
-    while (sbits < 32 && (1ull << sbits) <= (uint64_t)min(block_size, n)) ++sbits;
-    while (fbits < 32 && (1ull << fbits) <= (uint64_t)n) ++fbits;
-    if (sa_depth < 32) sa_depth = 32;
-    // round h = 8: every slot takes part (text: 71 % of the positions still share their 8 bytes with another one)
-    {
-        uint32_t* const rk32 = reinterpret_cast<uint32_t*>(rp8);     // rank at rk32[0..n), left-neighbour distance at rk32[n..2n)
-        hipLaunchKernelGGL(k_sa_rank_seq, dim3(g), dim3(256), 0, st, pos, grp, n, reinterpret_cast<uint2*>(key64_a));
-        e = invert_perm<uint64_t>(pos, pos_alt, key64_a, key64_b, n, rk32, rk32 + n, sort_tmp, tb, st);
-        if (e != hipSuccess) return (int)e;
-        // keys in position order (values = iota): both `pos` buffers are free again
-        hipLaunchKernelGGL(k_sa_pair_keys_pos, dim3(g), dim3(256), 0, st, rk32, n, block_size, 8u, sbits, key64_a, pos);
-        rocprim::double_buffer<uint64_t> kk(key64_a, key64_b);
-        rocprim::double_buffer<uint32_t> vv(pos, pos_alt);
-        e = rocprim::radix_sort_pairs(sort_tmp, tb, kk, vv, (size_t)n, 0u, sbits + fbits, st);
-        if (e != hipSuccess) return (int)e;
-        pos = vv.current();
-        pos_alt = vv.alternate();
-        hipLaunchKernelGGL(k_sa_flags64, dim3(g), dim3(256), 0, st, kk.current(), n, 0u, grp);
-        e = rocprim::inclusive_scan(sort_tmp, tb, grp, grp, (size_t)n, rocprim::maximum<uint32_t>(), st);
-        if (e != hipSuccess) return (int)e;
-    }
-    // rounds h = 16, 32, ...: by-position rank in rkpos (kept up to date by the compact rounds), slots in pos, groups in grp
-    uint32_t* const rkpos = reinterpret_cast<uint32_t*>(rp16);
-    uint32_t* const idx = keys_b;                     // free since round 0
-    uint32_t* const d_count = reinterpret_cast<uint32_t*>(key64_b);
-    bool rank_valid = false;
-    const char* const cenv = getenv("XZAMD_SA_COMPACT");          // 0: every round orders all slots (measurement knob)
-    const bool compact_on = !(cenv && *cenv == '0');
-    for (uint32_t h = 16; 2 * h <= sa_depth; h *= 2) {
-        const bool more = 4 * h <= sa_depth;
-        if (h == 16) {
-            // (rank, distance to the left neighbour inside the 16-byte group) of every slot, brought to position order;
-            // the slot order itself stays (the inversion works on a copy of it)
-            hipLaunchKernelGGL(k_sa_rank_seq, dim3(g), dim3(256), 0, st, pos, grp, n, reinterpret_cast<uint2*>(key64_a));
-            e = hipMemcpyAsync(idx, pos, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return (int)e;
-            e = invert_perm<uint64_t>(idx, sa, key64_a, key64_b, n, rkpos, rkpos + n, sort_tmp, tb, st);
-            if (e != hipSuccess) return (int)e;
-            rank_valid = true;
-        } else if (!rank_valid) {
-            uint32_t* const ra = reinterpret_cast<uint32_t*>(key64_a);
-            uint32_t* const rb = reinterpret_cast<uint32_t*>(key64_b);
-            hipLaunchKernelGGL(k_sa_rank_only_seq, dim3(g), dim3(256), 0, st, grp, n, ra);
-            e = hipMemcpyAsync(idx, pos, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return (int)e;
-            e = invert_perm<uint32_t>(idx, sa, ra, rb, n, rkpos, nullptr, sort_tmp, tb, st);
-            if (e != hipSuccess) return (int)e;
-            rank_valid = true;
-        }
-        uint32_t m = n;
-        if (compact_on && n >= 2) {
-            // how many slots are still undecided?  (One word back to the host: the sort below is sized by it.)
-            hipLaunchKernelGGL(k_sa_unres, dim3(g), dim3(256), 0, st, grp, n, idx);
-            e = rocprim::exclusive_scan(nullptr, need, idx, idx, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
-            if (e != hipSuccess) return (int)e;
-            if (need > tb) return (int)hipErrorOutOfMemory;
-            e = rocprim::exclusive_scan(sort_tmp, tb, idx, idx, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k_sa_count, dim3(1), dim3(1), 0, st, idx, grp, n, d_count);
-            e = hipMemcpyAsync(&m, d_count, 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return (int)e;
-            if (m == 0) break;                        // every suffix is distinguished: the order is final
-        }
-        if (h == 16 && prev24 != nullptr && compact_on && n >= 2) {
-            // prev24 (the nearest earlier position with the same 24 bytes): the members of the 16-byte groups once more,
-            // ordered by (group, rank after 8 bytes of p + 16) -- an extra sort of the m undecided slots only; the key,
-            // value and slot buffers of the compact round below are free until it runs
-            uint32_t* const cslot = pos_alt;
-            hipLaunchKernelGGL(k_sa_compact, dim3(g), dim3(256), 0, st, pos, grp, idx, reinterpret_cast<const uint32_t*>(rp8), n,
-                    block_size, 16u, sbits, key64_a, sa, cslot);
-            rocprim::double_buffer<uint64_t> kk(key64_a, key64_b);
-            rocprim::double_buffer<uint32_t> vv(sa, sa_rank);
-            e = rocprim::radix_sort_pairs(nullptr, need, kk, vv, (size_t)m, 0u, sbits + fbits, st);
-            if (e != hipSuccess) return (int)e;
-            if (need > tb) return (int)hipErrorOutOfMemory;
-            e = rocprim::radix_sort_pairs(sort_tmp, tb, kk, vv, (size_t)m, 0u, sbits + fbits, st);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k_sa_prev_scatter, dim3(grid_for(m, 256, 256 * 16)), dim3(256), 0, st, kk.current(), vv.current(), m, prev24);
-        }
-        if (compact_on && n >= 2 && (uint64_t)m * 10 <= (uint64_t)n * 6) {
-            uint32_t* const cslot = pos_alt;
-            const uint32_t gm = grid_for(m, 256, 256 * 16);
-            hipLaunchKernelGGL(k_sa_compact, dim3(g), dim3(256), 0, st, pos, grp, idx, rkpos, n, block_size, h, sbits,
-                    key64_a, sa, cslot);
-            rocprim::double_buffer<uint64_t> kk(key64_a, key64_b);
-            rocprim::double_buffer<uint32_t> vv(sa, sa_rank);
-            e = rocprim::radix_sort_pairs(sort_tmp, tb, kk, vv, (size_t)m, 0u, sbits + fbits, st);
-            if (e != hipSuccess) return (int)e;
-            if (h == 16 && prev32 != nullptr)         // by-product: the 32-byte groups' left neighbours
-                hipLaunchKernelGGL(k_sa_prev_scatter, dim3(gm), dim3(256), 0, st, kk.current(), vv.current(), m, prev32);
-            hipLaunchKernelGGL(k_sa_newgrp, dim3(gm), dim3(256), 0, st, kk.current(), cslot, m, idx);
-            e = rocprim::inclusive_scan(sort_tmp, tb, idx, idx, (size_t)m, rocprim::maximum<uint32_t>(), st);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k_sa_writeback, dim3(gm), dim3(256), 0, st, vv.current(), cslot, idx, m, pos, grp, rkpos);
-        } else {
-            // most slots are undecided (highly repetitive data): the full round, keys made in position order
-            hipLaunchKernelGGL(k_sa_pair_keys_pos, dim3(g), dim3(256), 0, st, rkpos, n, block_size, h, sbits, key64_a, pos);
-            rocprim::double_buffer<uint64_t> kk(key64_a, key64_b);
-            rocprim::double_buffer<uint32_t> vv(pos, pos_alt);
-            e = rocprim::radix_sort_pairs(sort_tmp, tb, kk, vv, (size_t)n, 0u, sbits + fbits, st);
-            if (e != hipSuccess) return (int)e;
-            pos = vv.current();
-            pos_alt = vv.alternate();
-            if (h == 16 && prev32 != nullptr)
-                hipLaunchKernelGGL(k_sa_prev_scatter, dim3(g), dim3(256), 0, st, kk.current(), pos, n, prev32);
-            if (more) {            // another round follows: its ranks need the groups of this order
-                hipLaunchKernelGGL(k_sa_flags64, dim3(g), dim3(256), 0, st, kk.current(), n, 0u, grp);
-                e = rocprim::inclusive_scan(sort_tmp, tb, grp, grp, (size_t)n, rocprim::maximum<uint32_t>(), st);
-                if (e != hipSuccess) return (int)e;
-            }
-            rank_valid = false;
-        }
-    }
-    // sa = slot order; sa_rank = its inverse (grp = keys_a is dead: scratch of the inversion)
-    hipLaunchKernelGGL(k_sa_final_seq, dim3(g), dim3(256), 0, st, pos, n, sa, sa_rank);
-    e = invert_perm<uint32_t>(pos, pos_alt, sa_rank, keys_a, n, sa_rank, nullptr, sort_tmp, tb, st);
-    if (e != hipSuccess) return (int)e;
-    return (int)hipGetLastError();
-}
-
-int xzk_find_matches(const xzamd_span_args* a, const uint32_t* sa, const uint32_t* sa_rank, const uint32_t* prev4,
-        const uint64_t* rp8, const uint64_t* rp16, const uint32_t* prev24, const uint32_t* prev32,
-        uint16_t* mlen, uint32_t* mdist, int part, void* stream_)
-{
-    hipStream_t st = (hipStream_t)stream_;
-    const uint32_t runs = (a->n + FIND_RUN - 1) / FIND_RUN;
-    if (runs == 0) return 0;
-    if (a->sa_window) {
-        if (!sa || !sa_rank || !prev4 || !rp8 || !rp16 || !prev24 || !prev32 || !a->mtop || a->sa_window > SN_WMAX)
-            return (int)hipErrorInvalidValue;
-        if (part != 0 && a->block_size < XZAMD_SEED_LEN + 2 * FIND_RUN) return (int)hipErrorInvalidValue;
-        SnArgs sn;
-        sn.in = a->in; sn.sa = sa; sn.sa_rank = sa_rank; sn.prev2 = a->prev2; sn.prev4 = prev4;
-        sn.prev8 = reinterpret_cast<const uint32_t*>(rp8) + a->n;     // second array of the round's (rank, distance) pair
-        sn.prev16 = reinterpret_cast<const uint32_t*>(rp16) + a->n;
-        sn.prev24 = prev24; sn.prev32 = prev32;
-        sn.mode = (uint32_t)part;
-        const uint32_t nblocks = (a->n + a->block_size - 1) / a->block_size;
-        hipLaunchKernelGGL(k_find_sn, dim3(part == 1 ? nblocks * SEED_RUNS : runs), dim3(64), 0, st, *a, sn, mlen, mdist);
-    } else {
-        hipLaunchKernelGGL(k_find_exact, dim3(runs), dim3(64), 0, st, *a, mlen, mdist);
-    }
-    return (int)hipGetLastError();
-}
-
-int xzk_span_plan(const xzamd_span_args* a, uint32_t nblocks, uint32_t* est, unsigned long long* totals,
-        uint32_t* span_tab, uint32_t* span_cnt, uint32_t cost_min, uint32_t bits_min, uint32_t min_len,
-        uint32_t* enc_tab, uint32_t* enc_cnt,
-        uint32_t* order_bufs, void* sort_tmp, uint64_t sort_tmp_bytes, uint32_t** order_out, void* stream_)
-{
-    hipStream_t st = (hipStream_t)stream_;
-    if (order_out) *order_out = nullptr;
-    if (nblocks == 0 || a->n == 0) return 0;
-    if (!a->mtop || a->max_spb == 0 || cost_min == 0 || !order_bufs || !order_out) return (int)hipErrorInvalidValue;
-    if (a->enc_bits && (!enc_tab || !enc_cnt || a->max_esb == 0 || min_len < XZAMD_SEED_LEN)) return (int)hipErrorInvalidValue;
-    const uint32_t cpb = (a->block_size + XZAMD_EST_CHUNK - 1) / XZAMD_EST_CHUNK;
-    const uint32_t nslots = nblocks * a->max_spb;
-    uint32_t* key_a = order_bufs;
-    uint32_t* key_b = order_bufs + nslots;
-    uint32_t* val_a = order_bufs + 2ull * nslots;
-    uint32_t* val_b = order_bufs + 3ull * nslots;
-    hipError_t e = hipMemsetAsync(totals, 0, (size_t)(nblocks + 2) * sizeof(unsigned long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(key_a, 0xFF, (size_t)nslots * 4, st);
-    if (e != hipSuccess) return (int)e;
-    const uint64_t nch = (uint64_t)nblocks * cpb;
-    hipLaunchKernelGGL(k_span_est, dim3((uint32_t)((nch + 255) / 256)), dim3(256), 0, st, *a, nblocks, cpb, est, totals);
-    hipLaunchKernelGGL(k_span_cut, dim3(nblocks), dim3(64), 0, st, *a, nblocks, cpb, est, totals, span_tab, span_cnt,
-            cost_min, bits_min, min_len, enc_tab, enc_cnt, key_a);
-    if (a->part_tab) {
-        xzamd_span_args a2 = *a;
-        a2.span_tab = span_tab; a2.span_cnt = span_cnt;
-        hipLaunchKernelGGL(k_part_ends, dim3((nslots + 255) / 256), dim3(256), 0, st, a2, nblocks, cpb, est, a->part_tab);
-    }
-    // launch order: span slots by estimated work, heaviest first (a launch then ends with its short spans instead of
-    // waiting for a heavy one that happened to start late); the order does not change a byte of the output
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(nslots, 256, 4096)), dim3(256), 0, st, val_a, nslots);
-    rocprim::double_buffer<uint32_t> kb(key_a, key_b);
-    rocprim::double_buffer<uint32_t> vb(val_a, val_b);
-    size_t need = 0;
-    e = rocprim::radix_sort_pairs(nullptr, need, kb, vb, (size_t)nslots, 0u, 32u, st);
-    if (e != hipSuccess) return (int)e;
-    if (need > sort_tmp_bytes) return (int)hipErrorOutOfMemory;
-    size_t tb = (size_t)sort_tmp_bytes;
-    e = rocprim::radix_sort_pairs(sort_tmp, tb, kb, vb, (size_t)nslots, 0u, 32u, st);
-    if (e != hipSuccess) return (int)e;
-    *order_out = vb.current();
-    return (int)hipGetLastError();
-}
 
 // waves = 0: one wavefront per span; else a persistent launch of min(waves, nspans) wavefronts that pull
 // span numbers from *counter (must be zero at launch).
@@ -4970,79 +2784,6 @@ int xzk_span_occupancy(int parser, uint32_t nice_len, int* waves_per_cu)
     return (int)e;
 }
 
-int xzk_x86_bcj(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, void* stream_)
-{
-    hipStream_t st = (hipStream_t)stream_;
-    int e = (int)hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, st);
-    if (e) return e;
-    const uint32_t cpb = (block_size + BCJ_CHUNK - 1) / BCJ_CHUNK;
-    const uint64_t nch = (uint64_t)cpb * nblocks;
-    if (nch == 0 || nch > 0xFFFFFFFFull) return nch ? (int)hipErrorInvalidValue : 0;
-    hipLaunchKernelGGL(k_x86_bcj, dim3((uint32_t)((nch + 255) / 256)), dim3(256), 0, st, d_in, d_out, n, block_size, cpb,
-            (uint32_t)nch);
-    return (int)hipGetLastError();
-}
-
-// prefilter kind: 0x0A = ARM64 BCJ, 0x0B = RISC-V BCJ, 5 / 6 / 7 / 8 / 9 = PowerPC / IA-64 / ARM / ARM-Thumb / SPARC BCJ, 3 = delta (dist 1..256):
-// d_out = filtered copy of d_in
-int xzk_prefilter(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t kind, uint32_t dist,
-        void* stream_)
-{
-    hipStream_t st = (hipStream_t)stream_;
-    if (n == 0) return 0;
-    if (kind == 0x0A) {
-        int e = (int)hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, st);
-        if (e) return e;
-        hipLaunchKernelGGL(k_arm64_bcj, dim3(grid_for((uint64_t)n / 4 + 1, 256, 65536)), dim3(256), 0, st, d_in, d_out, n, block_size, nblocks);
-    } else if (kind == 0x0B) {
-        int e = (int)hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, st);
-        if (e) return e;
-        const uint32_t cpb = (block_size + BCJ_CHUNK - 1) / BCJ_CHUNK;
-        const uint64_t nch = (uint64_t)cpb * nblocks;
-        if (nch > 0xFFFFFFFFull) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_riscv_bcj, dim3((uint32_t)((nch + 255) / 256)), dim3(256), 0, st, d_in, d_out, n, block_size, cpb,
-                (uint32_t)nch);
-    } else if (kind >= 5 && kind <= 9) {
-        int e = (int)hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, st);
-        if (e) return e;
-        hipLaunchKernelGGL(k_bcj_simple, dim3(grid_for((uint64_t)n / 2 + 1, 256, 65536)), dim3(256), 0, st, d_in, d_out, n, block_size,
-                nblocks, kind);
-    } else if (kind == 3) {
-        hipLaunchKernelGGL(k_delta, dim3(grid_for(n, 256, 65536)), dim3(256), 0, st, d_in, d_out, n, block_size, dist);
-    } else {
-        return (int)hipErrorInvalidValue;
-    }
-    return (int)hipGetLastError();
-}
-
-int xzk_sha256_blocks(const uint8_t* d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint8_t* d_out32, void* stream_)
-{
-    if (nblocks == 0) return 0;
-    hipLaunchKernelGGL(k_sha256_blocks, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_in, n, block_size, nblocks, d_out32);
-    return (int)hipGetLastError();
-}
-
-int xzk_crc_blocks(const uint8_t* d_in, uint32_t n, uint32_t block_size, uint32_t nblocks,
-        uint32_t strip, int crc32, uint64_t* d_strip_crc, uint64_t* d_block_crc, void* stream_)
-{
-    hipStream_t st = (hipStream_t)stream_;
-    const uint32_t spb = (block_size + strip - 1) / strip;
-    const uint32_t ns = spb * nblocks;
-    if (crc32) {
-        uint32_t* strips = reinterpret_cast<uint32_t*>(d_strip_crc);
-        hipLaunchKernelGGL((k_crc_strips<uint32_t>), dim3((ns + 255) / 256), dim3(256), 0, st, d_in, n, block_size, strip,
-                spb, ns, strips);
-        hipLaunchKernelGGL((k_crc_fold<uint32_t>), dim3(nblocks), dim3(64), 0, st, strips, n, block_size, strip, spb,
-                d_block_crc);
-    } else {
-        hipLaunchKernelGGL((k_crc_strips<uint64_t>), dim3((ns + 255) / 256), dim3(256), 0, st, d_in, n, block_size, strip,
-                spb, ns, d_strip_crc);
-        hipLaunchKernelGGL((k_crc_fold<uint64_t>), dim3(nblocks), dim3(64), 0, st, d_strip_crc, n, block_size, strip, spb,
-                d_block_crc);
-    }
-    return (int)hipGetLastError();
-}
-
 int xzk_assemble(const xzamd_copy_seg* d_segs, uint32_t nsegs, const uint8_t* d_scratch, const uint8_t* d_lits,
         const uint8_t* d_in, uint8_t* d_out, void* stream_)
 {
@@ -5050,43 +2791,6 @@ int xzk_assemble(const xzamd_copy_seg* d_segs, uint32_t nsegs, const uint8_t* d_
     if (nsegs == 0) return 0;
     hipLaunchKernelGGL(k_assemble, dim3(nsegs), dim3(256), 0, st, d_segs, nsegs, d_scratch, d_lits, d_in, d_out);
     return (int)hipGetLastError();
-}
-
-// --- thin runtime shims so the plain-C host layer needs no HIP headers ---------------------
-int xzk_malloc(void** p, uint64_t bytes) { return (int)hipMalloc(p, bytes); }
-int xzk_free(void* p) { return (int)hipFree(p); }
-int xzk_host_alloc(void** p, uint64_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
-int xzk_host_free(void* p) { return (int)hipHostFree(p); }
-int xzk_h2d(void* d, const void* h, uint64_t bytes, void* st) { return (int)hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, (hipStream_t)st); }
-int xzk_d2h(void* h, const void* d, uint64_t bytes, void* st) { return (int)hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, (hipStream_t)st); }
-int xzk_memset(void* d, int v, uint64_t bytes, void* st) { return (int)hipMemsetAsync(d, v, bytes, (hipStream_t)st); }
-int xzk_sync(void* st) { return (int)hipStreamSynchronize((hipStream_t)st); }
-int xzk_set_device(int dev) { return (int)hipSetDevice(dev); }
-int xzk_get_device(int* dev) { return (int)hipGetDevice(dev); }
-int xzk_device_count(int* n) { return (int)hipGetDeviceCount(n); }
-int xzk_cu_count(int dev, int* cus) { return (int)hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev); }
-int xzk_stream_create(void** st) { return (int)hipStreamCreateWithFlags((hipStream_t*)st, hipStreamNonBlocking); }
-// lowest-priority stream of the device (work on it only fills slots the caller's stream leaves free)
-int xzk_stream_create_low(void** st)
-{
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-    return (int)hipStreamCreateWithPriority((hipStream_t*)st, hipStreamNonBlocking, least);
-}
-int xzk_stream_wait_event(void* st, void* ev) { return (int)hipStreamWaitEvent((hipStream_t)st, (hipEvent_t)ev, 0); }
-int xzk_stream_destroy(void* st) { return (int)hipStreamDestroy((hipStream_t)st); }
-int xzk_event_create(void** ev) { return (int)hipEventCreate((hipEvent_t*)ev); }
-int xzk_event_destroy(void* ev) { return (int)hipEventDestroy((hipEvent_t)ev); }
-int xzk_event_record(void* ev, void* st) { return (int)hipEventRecord((hipEvent_t)ev, (hipStream_t)st); }
-int xzk_event_elapsed_ms(void* a, void* b, float* ms) { return (int)hipEventElapsedTime(ms, (hipEvent_t)a, (hipEvent_t)b); }
-int xzk_event_query(void* ev) { return (int)hipEventQuery((hipEvent_t)ev); }
-const char* xzk_error_string(int e) { return hipGetErrorString((hipError_t)e); }
-int xzk_mem_info(uint64_t* free_b, uint64_t* total_b)
-{
-    size_t f = 0, t = 0;
-    hipError_t e = hipMemGetInfo(&f, &t);
-    *free_b = f; *total_b = t;
-    return (int)e;
 }
 
 } // extern "C"

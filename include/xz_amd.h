@@ -230,7 +230,8 @@ int xzamd_stream_encode_device(xzamd_ctx *ctx,
 		void *stream);
 
 /* Device .xz decoder (the reference's stream_decoder_mt.c / lzma2_decoder.c / lzma_decoder.c path, SURVEY.md
- * 8f.3): decode a single-Stream .xz file resident in device memory into d_out.  Filter chains, per Block: {LZMA2} and
+ * 8f.3): decode a single-Stream .xz file resident in device memory into d_out (trailing bytes, Stream Padding or a second
+ * Stream are an error here: xzamd_file_decode_device reads those).  Filter chains, per Block: {LZMA2} and
  * {up to three of: delta (0x03) | x86, PowerPC, IA-64, ARM, ARM-Thumb, SPARC, ARM64, RISC-V BCJ (0x04 .. 0x0B), LZMA2};
  * declined with XZAMD_OPTIONS_ERROR: a BCJ start offset other than 0, any other filter id, any chain the reference's
  * lzma_validate_chain refuses.  A Stream with a filtered Block needs one or two temporaries of the uncompressed size.
@@ -243,6 +244,70 @@ int xzamd_stream_encode_device(xzamd_ctx *ctx,
 int xzamd_stream_decode_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, void *d_out, uint64_t out_cap,
 		uint64_t *out_size, const void *d_expected, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks,
 		void *stream);
+
+/* ---- whole .xz files: concatenated Streams, Stream Padding, file index, range decode ----
+ * An .xz file is one or more Streams, each followed by Stream Padding (zero bytes, a multiple of four): what `xz -d`
+ * and every liblzma client with LZMA_CONCATENATED read.  The file is walked from its end, as the reference's
+ * common/file_info.c does: Stream Padding, Stream Footer, Backward Size, Index; the padded Block sizes of the Index give
+ * the place of the Stream Header; in front of it lies the padding of the Stream before.  All framing of all Streams is
+ * validated before a Block is looked at, all Blocks before the first decode kernel runs.
+ * Codes (common/stream_decoder.c with LZMA_CONCATENATED): 7 (LZMA_FORMAT_ERROR) only for a file shorter than 32 bytes or
+ * without the Header Magic at offset 0; XZAMD_DATA_ERROR for every other framing defect (padding that is no multiple of
+ * four, bad magic of a Footer or of a later Header, a Backward Size or Block sizes that do not land on a Stream Header,
+ * Header and Footer that disagree); XZAMD_OPTIONS_ERROR for Stream Flags of an unknown version; XZAMD_UNSUPPORTED_CHECK
+ * for a Check without a verifier in any Stream; inside a Block the codes of xzamd_stream_decode_device.
+ * Streams may differ in Check and in filter chains; Streams without Blocks are legal. */
+typedef struct {
+	uint64_t offset;                /* of the Stream Header in the file */
+	uint64_t size;                  /* Stream Header .. Stream Footer */
+	uint64_t padding;               /* Stream Padding behind it */
+	uint64_t first_block;           /* index of its first Block in the Block list */
+	uint64_t block_count;
+	uint64_t uncompressed_offset;   /* of its first byte in the decoded file */
+	uint64_t uncompressed_size;
+	uint32_t check;                 /* XZAMD_CHECK_* */
+	uint32_t reserved_;
+} xzamd_xz_stream;
+
+typedef struct {
+	uint64_t header_offset;         /* of the Block Header in the file */
+	uint64_t unpadded_size;         /* Index record */
+	uint64_t total_size;            /* Unpadded Size rounded up to four: header + data + padding + check */
+	uint64_t uncompressed_size;     /* Index record */
+	uint64_t uncompressed_offset;   /* of its first byte in the decoded file */
+	uint32_t stream;                /* index of its Stream */
+	uint32_t filter_count;
+	uint32_t filter_ids[4];         /* in Block Header order, LZMA2 (0x21) last */
+} xzamd_xz_block;
+
+/* List the Streams and Blocks of a file (xz --list, lzma_file_info_decoder) and validate all of its framing: Stream
+ * Headers / Footers / Padding, Indexes, every Block Header, sizes against the Index, Block Padding.  *nstreams, *nblocks,
+ * *uncompressed_size are always filled in once the framing is valid; XZAMD_BUF_ERROR when a capacity is too small
+ * (streams / blocks may be NULL with capacity 0).  The host variant reads host memory and needs neither a GPU nor a
+ * context; the device variant reads device memory: three small reads per Stream, and one kernel (one thread per Block)
+ * for all Block Headers. */
+int xzamd_file_index_host(const void *xz, uint64_t xz_size, xzamd_xz_stream *streams, uint64_t streams_cap, uint64_t *nstreams,
+		xzamd_xz_block *blocks, uint64_t blocks_cap, uint64_t *nblocks, uint64_t *uncompressed_size);
+int xzamd_file_index_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, xzamd_xz_stream *streams, uint64_t streams_cap,
+		uint64_t *nstreams, xzamd_xz_block *blocks, uint64_t blocks_cap, uint64_t *nblocks, uint64_t *uncompressed_size);
+
+/* xzamd_stream_decode_device for a whole file: any number of Streams plus Stream Padding.  The Blocks of all Streams form
+ * one table and go through one scan and one decode launch; the Checks are verified per Stream.  With d_expected the
+ * span-parallel units of the verification decode are kept for a file of one Stream; a file of several Streams decodes
+ * Block by Block; the result is compared with the original either way.  *nblocks = Blocks of all Streams. */
+int xzamd_file_decode_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, void *d_out, uint64_t out_cap,
+		uint64_t *out_size, const void *d_expected, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks,
+		void *stream);
+
+/* Decode uncompressed bytes [uoffset, uoffset + ulen) of a file by decoding only the Blocks that hold them (and
+ * verifying their Checks): random access into an .xz file of small Blocks.  The range is clipped at the end of the file
+ * like pread: *out_size = bytes written at d_out (0 for an offset at or behind the end, or ulen 0: nothing is decoded).
+ * Stream framing and Indexes are validated for the whole file, Block framing for the Blocks that are decoded: a defect
+ * of another Block does not fail the call.  A range that starts and ends on Block boundaries decodes straight into
+ * d_out, any other into a temporary of the touched Blocks from which the range is copied.  *blocks_decoded = Blocks
+ * touched.  XZAMD_BUF_ERROR (with *out_size set) when out_cap is smaller than the clipped range. */
+int xzamd_file_decode_range_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, uint64_t uoffset, uint64_t ulen,
+		void *d_out, uint64_t out_cap, uint64_t *out_size, uint64_t *blocks_decoded, void *stream);
 
 /* Host-side framing helpers for the multi-GPU path: Stream Header (12 bytes),
  * Index + Stream Footer from gathered Block records. Return bytes written. */

@@ -52,6 +52,20 @@ class BlockInfo(C.Structure):
                 ("out_offset", C.c_uint64), ("total_size", C.c_uint64)]
 
 
+class XzStream(C.Structure):
+    """xzamd_xz_stream: one Stream of an .xz file."""
+    _fields_ = [(n, C.c_uint64) for n in ("offset", "size", "padding", "first_block", "block_count",
+                                          "uncompressed_offset", "uncompressed_size")] + \
+               [("check", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class XzBlock(C.Structure):
+    """xzamd_xz_block: one Block of an .xz file."""
+    _fields_ = [(n, C.c_uint64) for n in ("header_offset", "unpadded_size", "total_size", "uncompressed_size",
+                                          "uncompressed_offset")] + \
+               [("stream", C.c_uint32), ("filter_count", C.c_uint32), ("filter_ids", C.c_uint32 * 4)]
+
+
 _lib = None
 
 
@@ -96,6 +110,17 @@ def lib():
         l.xzamd_stream_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                  C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64), C.c_void_p]
+        if hasattr(l, "xzamd_file_index_host"):         # an older library (XZ_AMD_LIB, A/B runs) lacks the file entries
+            idx_args = [C.c_void_p, C.c_uint64, C.POINTER(XzStream), C.c_uint64, C.POINTER(C.c_uint64),
+                        C.POINTER(XzBlock), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            l.xzamd_file_index_host.argtypes = idx_args
+            l.xzamd_file_index_device.argtypes = [C.c_void_p] + idx_args
+            l.xzamd_file_decode_device.argtypes = l.xzamd_stream_decode_device.argtypes
+            l.xzamd_file_decode_range_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                         C.POINTER(C.c_uint64), C.c_void_p]
+            l.xzamd_debug_file_counters_.restype = None
+            l.xzamd_debug_file_counters_.argtypes = [C.POINTER(C.c_uint64)]
         l.xzamd_debug_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         l.xzamd_trace_enable.argtypes = [C.c_void_p, C.c_uint32]
         l.xzamd_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -149,7 +174,46 @@ def corpus_tar(n, roots=TAR_ROOTS, seed=1):
 
 
 class XzAmdError(RuntimeError):
-    pass
+    """`code` = the XZAMD_* / lzma_ret value of the failed call, where there is one."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
+
+
+def _stream_dict(s):
+    return {n: getattr(s, n) for n in ("offset", "size", "padding", "first_block", "block_count", "uncompressed_offset",
+                                       "uncompressed_size", "check")}
+
+
+def _block_dict(b):
+    d = {n: getattr(b, n) for n in ("header_offset", "unpadded_size", "total_size", "uncompressed_size",
+                                    "uncompressed_offset", "stream")}
+    d["filter_ids"] = tuple(b.filter_ids[: b.filter_count])
+    return d
+
+
+def _file_index(call, what, detail):
+    """Both variants of xzamd_file_index_*: ask for the counts, then for the lists.  Returns (streams, blocks,
+    uncompressed size), Streams and Blocks as dicts named like the fields of xzamd_xz_stream / xzamd_xz_block."""
+    ns, nb, usz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = call(None, 0, C.byref(ns), None, 0, C.byref(nb), C.byref(usz))
+    if rc not in (0, 10):
+        raise XzAmdError(f"{what} failed ({rc})" + detail(), rc)
+    streams, blocks = (XzStream * max(ns.value, 1))(), (XzBlock * max(nb.value, 1))()
+    rc = call(streams, ns.value, C.byref(ns), blocks, nb.value, C.byref(nb), C.byref(usz))
+    if rc != 0:
+        raise XzAmdError(f"{what} failed ({rc})" + detail(), rc)
+    return ([_stream_dict(s) for s in streams[: ns.value]], [_block_dict(b) for b in blocks[: nb.value]], usz.value)
+
+
+def file_index(xz_bytes):
+    """Streams and Blocks of an .xz file held in host memory (bytes): xz --list.  Validates all framing of the file
+    (Stream Headers / Footers / Padding, Indexes, Block Headers and Padding); needs no GPU.  Returns (streams, blocks,
+    uncompressed size)."""
+    buf = bytes(xz_bytes)
+    f = lib().xzamd_file_index_host
+    return _file_index(lambda *a: f(buf, len(buf), *a), "xzamd_file_index_host", lambda: "")
 
 
 class Encoder:
@@ -240,10 +304,66 @@ class Encoder:
             expected.numel() if expected is not None else 0, C.byref(mm), C.byref(nb), None)
         if rc != 0:
             raise XzAmdError(f"xzamd_stream_decode_device failed ({rc}): {lib().xzamd_last_error(self._ctx).decode()}"
-                             + (f" [{mm.value} mismatching words]" if mm.value else ""))
+                             + (f" [{mm.value} mismatching words]" if mm.value else ""), rc)
+        return out[: osz.value], nb.value
+
+    def _detail(self):
+        return ": " + lib().xzamd_last_error(self._ctx).decode()
+
+    def file_index(self, xz):
+        """Streams and Blocks of an .xz file held in a CUDA uint8 tensor: `file_index` with the Block Headers parsed on
+        the device (one thread per Block)."""
+        import torch
+        assert xz.is_cuda and xz.dtype == torch.uint8 and xz.is_contiguous()
+        torch.cuda.current_stream(xz.device).synchronize()
+        f = lib().xzamd_file_index_device
+        return _file_index(lambda *a: f(self._ctx, C.c_void_p(xz.data_ptr()), xz.numel(), *a), "xzamd_file_index_device",
+                           self._detail)
+
+    def decode_file(self, xz, out_cap, expected=None):
+        """`decode` for a whole .xz file: any number of Streams, each followed by Stream Padding.  Returns (decoded
+        tensor view, Blocks of all Streams)."""
+        import torch
+        assert xz.is_cuda and xz.dtype == torch.uint8 and xz.is_contiguous()
+        if expected is not None:
+            assert (expected.is_cuda and expected.dtype == torch.uint8 and expected.is_contiguous()
+                    and expected.device == xz.device), "expected: contiguous CUDA uint8 tensor on the file's device"
+        out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=xz.device)
+        osz, mm, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.current_stream(xz.device).synchronize()
+        rc = lib().xzamd_file_decode_device(
+            self._ctx, C.c_void_p(xz.data_ptr()), xz.numel(), C.c_void_p(out.data_ptr()), out_cap, C.byref(osz),
+            C.c_void_p(expected.data_ptr()) if expected is not None else None,
+            expected.numel() if expected is not None else 0, C.byref(mm), C.byref(nb), None)
+        if rc != 0:
+            raise XzAmdError(f"xzamd_file_decode_device failed ({rc})" + self._detail()
+                             + (f" [{mm.value} mismatching words]" if mm.value else ""), rc)
+        return out[: osz.value], nb.value
+
+    def decode_range(self, xz, offset, length):
+        """Uncompressed bytes [offset, offset + length) of an .xz file, clipped at its end like pread; only the Blocks
+        that hold them are decoded (and their Checks verified).  Returns (tensor of the bytes, Blocks decoded)."""
+        import torch
+        assert xz.is_cuda and xz.dtype == torch.uint8 and xz.is_contiguous()
+        out = torch.empty(max(length, 1), dtype=torch.uint8, device=xz.device)
+        osz, nb = C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.current_stream(xz.device).synchronize()
+        rc = lib().xzamd_file_decode_range_device(
+            self._ctx, C.c_void_p(xz.data_ptr()), xz.numel(), offset, length, C.c_void_p(out.data_ptr()), length,
+            C.byref(osz), C.byref(nb), None)
+        if rc != 0:
+            raise XzAmdError(f"xzamd_file_decode_range_device failed ({rc})" + self._detail(), rc)
         return out[: osz.value], nb.value
 
     # debug hooks used by the parity tests
+    @staticmethod
+    def debug_file_counters():
+        """Counts of the last file call on a file in device memory (test instrumentation): (device-to-host reads,
+        kernel-launch calls, Blocks decoded)."""
+        a = (C.c_uint64 * 3)()
+        lib().xzamd_debug_file_counters_(a)
+        return tuple(a)
+
     @staticmethod
     def debug_decode_counters():
         """Process-wide counts of the device decoder (test instrumentation): (temporary buffers allocated for inverse

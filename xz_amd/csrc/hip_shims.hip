@@ -12,6 +12,7 @@ int xzk_host_alloc(void** p, uint64_t bytes) { return (int)hipHostMalloc(p, byte
 int xzk_host_free(void* p) { return (int)hipHostFree(p); }
 int xzk_h2d(void* d, const void* h, uint64_t bytes, void* st) { return (int)hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, (hipStream_t)st); }
 int xzk_d2h(void* h, const void* d, uint64_t bytes, void* st) { return (int)hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, (hipStream_t)st); }
+int xzk_d2d(void* d, const void* s, uint64_t bytes, void* st) { return (int)hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, (hipStream_t)st); }
 int xzk_memset(void* d, int v, uint64_t bytes, void* st) { return (int)hipMemsetAsync(d, v, bytes, (hipStream_t)st); }
 int xzk_sync(void* st) { return (int)hipStreamSynchronize((hipStream_t)st); }
 int xzk_set_device(int dev) { return (int)hipSetDevice(dev); }

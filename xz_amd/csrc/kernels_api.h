@@ -259,6 +259,30 @@ typedef struct {
 #define XZAMD_UNF_DELTA 4u
 int xzk_dec_unfilter(const xzamd_unf_args *a, uint32_t total_tiles, uint32_t kinds, void *stream);
 
+/* ---- per-Block framing of a whole .xz file on the device (k_dec_headers, lzma_decode.hip) ----
+ * The host parses the Indexes (their VLIs are serial) and uploads one record per Block; one thread per Block then runs
+ * xzb_block (xzamd_block_parse.h) over d_xz: Block Header, sizes against the Index, Block Padding, the stored Check. */
+typedef struct {
+	uint64_t hpos;       /* offset of the Block Header in the file */
+	uint64_t unpadded;   /* Unpadded Size of the Index record */
+	uint64_t usize;      /* Uncompressed Size of the Index record */
+	uint64_t end;        /* where the Blocks of its Stream end (= its Index starts): no read at or behind it */
+	uint64_t upos;       /* where the Block's bytes go in the output */
+	uint32_t csz;        /* size of the Check of its Stream */
+	uint32_t pad_;
+} xzamd_hdr_rec;
+typedef struct {
+	uint32_t code;       /* 0 or the error code of the Block's first defect */
+	uint32_t step;       /* XZB_S_*: the check that failed */
+} xzamd_hdr_err;
+#define XZAMD_HDR_CHECK_BYTES 32u       /* stored Check per Block in the table (the longest Check with a verifier: SHA-256) */
+/* d_table (xzk_dec_headers writes it, one read-back brings it to the host): nblocks x xzamd_dec_block, then nblocks x
+ * xzamd_dec_chain, then nblocks x XZAMD_HDR_CHECK_BYTES, then nblocks x xzamd_hdr_err */
+#define XZAMD_HDR_TABLE_BYTES(n) ((uint64_t)(n) * (sizeof(xzamd_dec_block) + sizeof(xzamd_dec_chain) + XZAMD_HDR_CHECK_BYTES + sizeof(xzamd_hdr_err)))
+/* every record must have hpos <= end <= xz_size: the kernel bounds its reads by `end` */
+int xzk_dec_headers(const uint8_t *d_xz, uint64_t xz_size, const xzamd_hdr_rec *d_recs, uint32_t nblocks, void *d_table, void *stream);
+
+int xzk_d2d(void *dst, const void *src, uint64_t bytes, void *stream);
 int xzk_malloc(void **p, uint64_t bytes);
 int xzk_free(void *p);
 int xzk_host_alloc(void **p, uint64_t bytes);

@@ -21,6 +21,7 @@
 #include "kernels_api.h"
 #include "wave.h"
 #include "bcj_rules.h"
+#include "xzamd_block_parse.h"
 
 namespace {
 
@@ -86,6 +87,33 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
     if (err == DEC_OK && (!ended || c != B.csize || u != B.usize)) err = DEC_SIZE_MISMATCH;
     B.nunits = nunits;
     B.error = err;
+}
+
+// One thread per Block of a whole .xz file (any number of Streams): what the host loop of xzamd_stream_decode_device
+// does per Block with three device-to-host reads -- Block Header (size byte, CRC32, flags, VLIs, Filter Flags, padding,
+// chain rule), sizes against the Index record, Block Padding, the stored Check -- in the same order (xzb_block is that
+// loop's text), so that the first defect of a Block gives the code the host parser gives.  Latency-bound table work:
+// every thread reads a few dozen bytes of its own Block, one upload / launch / read-back per file instead of three
+// synchronous reads per Block.  No read outside [hpos, end) of the Block's record, and `end` is clamped to the file.
+__global__ __launch_bounds__(64) void k_dec_headers(const uint8_t* __restrict__ xz, uint64_t xz_size,
+        const xzamd_hdr_rec* __restrict__ recs, uint32_t nblocks, xzamd_dec_block* __restrict__ blocks,
+        xzamd_dec_chain* __restrict__ chains, uint8_t* __restrict__ stored, xzamd_hdr_err* __restrict__ errs)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nblocks) return;
+    xzamd_hdr_rec r = recs[b];
+    xzamd_dec_block B;
+    xzamd_dec_chain ch;
+    uint32_t step = XZB_S_NONE, code;
+    if (r.end > xz_size) {
+        // a record the host must never write: nothing of the file is read for it
+        r.hpos = r.end = 0;
+    }
+    code = xzb_block(xz, &r, &B, &ch, stored + (uint64_t)b * XZAMD_HDR_CHECK_BYTES, &step);
+    blocks[b] = B;
+    chains[b] = ch;
+    errs[b].code = code;
+    errs[b].step = step;
 }
 
 // ---- range decoder + LZMA symbol decoder, wave-uniform -------------------------------------------------
@@ -840,6 +868,19 @@ int xzk_dec_scan(const uint8_t* d_xz, xzamd_dec_block* d_blocks, uint32_t nblock
     if (nblocks == 0) return 0;
     hipLaunchKernelGGL(k_dec_scan, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_xz, d_blocks, nblocks,
             d_units, units_cap, split);
+    return (int)hipGetLastError();
+}
+
+int xzk_dec_headers(const uint8_t* d_xz, uint64_t xz_size, const xzamd_hdr_rec* d_recs, uint32_t nblocks, void* d_table, void* stream_)
+{
+    if (nblocks == 0) return 0;
+    uint8_t* t = (uint8_t*)d_table;
+    xzamd_dec_block* blocks = (xzamd_dec_block*)t;
+    xzamd_dec_chain* chains = (xzamd_dec_chain*)(blocks + nblocks);
+    uint8_t* stored = (uint8_t*)(chains + nblocks);
+    xzamd_hdr_err* errs = (xzamd_hdr_err*)(stored + (uint64_t)nblocks * XZAMD_HDR_CHECK_BYTES);
+    hipLaunchKernelGGL(k_dec_headers, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_xz, xz_size, d_recs, nblocks,
+            blocks, chains, stored, errs);
     return (int)hipGetLastError();
 }
 

@@ -18,7 +18,9 @@
  *   check/crc32_fast.c, crc64_fast.c        -> the encoder's k_crc_strips / k_crc_fold over the decoded bytes
  * Scheduling model of common/stream_decoder_mt.c: independent Blocks in parallel; with the original data at
  * hand (verification) every state-resetting chunk chain is its own unit.
- * Supported: one Stream; the filter chains {LZMA2} and {up to three of: delta | x86 | PowerPC | IA-64 | ARM | ARM-Thumb |
+ * The device part (unit scan, decode, inverse filters, Checks, comparison) is xzamd_dec_run_, which the whole-file entries of
+ * xzamd_file.c run over the Blocks of several Streams; the per-Block header checks are xzb_header (xzamd_block_parse.h).
+ * Supported here: one Stream; the filter chains {LZMA2} and {up to three of: delta | x86 | PowerPC | IA-64 | ARM | ARM-Thumb |
  * SPARC | ARM64 | RISC-V, LZMA2}, which may differ from Block to Block; checks none / CRC32 / CRC64 / SHA-256, all
  * verified.  Declined with XZAMD_OPTIONS_ERROR: a BCJ filter with a non-zero start offset (nothing in this project
  * writes one), every other filter id, every chain the reference's lzma_validate_chain refuses.
@@ -32,6 +34,7 @@
  */
 #include "xzamd_internal.h"
 #include "kernels_api.h"
+#include "xzamd_block_parse.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -47,210 +50,65 @@ void xzamd_debug_decode_counters_(uint64_t out[3])
 }
 static void count_(int i) { __atomic_fetch_add(&dec_counters[i], 1, __ATOMIC_RELAXED); }
 
-static int vli_get(const uint8_t *p, size_t n, size_t *pos, uint64_t *v)
-{
-	/* common/vli_decoder.c:16-86 (single call form) */
-	uint64_t r = 0;
-	for (unsigned i = 0; i < 9; ++i) {
-		if (*pos >= n) return -1;
-		const uint8_t b = p[(*pos)++];
-		r |= (uint64_t)(b & 0x7F) << (7 * i);
-		if (!(b & 0x80)) {
-			if (b == 0 && i != 0) return -1;        /* non-minimal encoding */
-			*v = r;
-			return 0;
-		}
-	}
-	return -1;
-}
+static void reads_(const xzamd_dec_job *j, uint64_t n) { if (j->counts) j->counts[0] += n; }
+static void launches_(const xzamd_dec_job *j, uint64_t n) { if (j->counts) j->counts[1] += n; }
 
+const char *xzamd_block_step_msg_(uint32_t step)
+{
+	static const char *const msg[XZB_S_COUNT] = {
+		"", "Block beyond the Index", "Index indicator where a Block Header was expected", "Block Header beyond the Index",
+		"Block Header CRC32", "reserved Block Flags", "Block Header Compressed Size", "Block Header Uncompressed Size", "Filter Flags",
+		"LZMA2 properties (dictionary size byte)", "delta filter: size of properties", "BCJ filter: size of properties",
+		"BCJ filter with a non-zero start offset is not decoded on the device", "filter id the device decoder does not know",
+		"Block Header padding", "filter chain: LZMA2 must be the last filter and only the last",
+		"Unpadded Size smaller than its header", "Block Header sizes differ from the Index", "Block beyond the Index",
+		"Block Padding", "Block too large for the device decoder" };
+	return step < XZB_S_COUNT ? msg[step] : "";
+}
 static uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 #define FAILD(code, msg) do { rc = xzamd_ctx_fail_(c, (code), (msg)); goto done; } while (0)
 #define HIPD(call, msg) do { if (call) FAILD(XZAMD_DEVICE_ERROR, msg); } while (0)
 
-int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size, void *d_out_, uint64_t out_cap,
-		uint64_t *out_size, const void *d_expected_, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks_out,
-		void *stream)
+/* The device part of a decode: the Blocks of j->hb (parsed and validated: xzb_block) through unit scan, LZMA2 decode,
+ * inverse filters, Checks (per group of Blocks = per Stream) and the comparison with the original. */
+int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 {
-	if (!c || !d_xz_ || !out_size || (!d_out_ && out_cap))
-		return XZAMD_PROG_ERROR;
-	const uint8_t *d_xz = (const uint8_t *)d_xz_;
-	uint8_t *d_out = (uint8_t *)d_out_;
-	const uint8_t *d_expected = (const uint8_t *)d_expected_;
-	void *st = stream ? stream : xzamd_ctx_stream_(c);
+	const uint8_t *d_xz = j->d_xz;
+	uint8_t *d_out = j->d_out;
+	const uint8_t *d_expected = j->d_expected;
+	const uint64_t nb = j->nb;
+	xzamd_dec_block *hb = j->hb;
+	const xzamd_dec_chain *hc = j->hc;
+	uint64_t *mismatches = j->mismatches;
 	int rc = XZAMD_OK;
-	uint8_t *index = NULL;
-	xzamd_dec_block *hb = NULL;
-	uint64_t *stored = NULL, *h_crc = NULL;
-	uint8_t *stored32 = NULL;          /* SHA-256: the 32 stored bytes of every Block */
+	uint64_t *h_crc = NULL;
+	uint8_t *h_sha = NULL;
 	void *d_sha = NULL;
 	uint32_t *unit_first = NULL, *h_err = NULL;
 	void *d_blocks = NULL, *d_units = NULL, *d_first = NULL, *d_lit = NULL, *d_misc = NULL, *d_strip = NULL, *d_crc = NULL;
-	xzamd_dec_chain *hc = NULL;        /* per Block: the filters in front of LZMA2 */
 	uint32_t *tile_first = NULL;
 	void *d_chains = NULL, *d_tiles = NULL, *d_t0 = NULL, *d_t1 = NULL, *d_filt = NULL, *d_tsum = NULL, *d_tcarry = NULL;
 	uint32_t max_nf = 0;
 	int any_filtered = 0, any_plain = 0;
-	*out_size = 0;
-	if (mismatches) *mismatches = 0;
-	if (nblocks_out) *nblocks_out = 0;
-	if (xzk_set_device(xzamd_ctx_device(c)))
-		return xzamd_ctx_fail_(c, XZAMD_DEVICE_ERROR, "hipSetDevice");
-
-	/* Stream Header + Footer */
-	static const uint8_t magic[6] = { 0xFD, '7', 'z', 'X', 'Z', 0x00 };
-	uint8_t hf[24];
-	if (xz_size < 32 || (xz_size & 3))
-		FAILD(FORMAT_ERROR, "not an .xz Stream (size)");
-	HIPD(xzk_d2h(hf, d_xz, 12, st) || xzk_d2h(hf + 12, d_xz + xz_size - 12, 12, st) || xzk_sync(st), "d2h stream flags");
-	if (memcmp(hf, magic, 6) != 0 || hf[22] != 'Y' || hf[23] != 'Z')
-		FAILD(FORMAT_ERROR, "bad magic bytes");
-	if (rd32(hf + 8) != xzamd_crc32_host_(hf + 6, 2) || rd32(hf + 12) != xzamd_crc32_host_(hf + 16, 6))
-		FAILD(XZAMD_DATA_ERROR, "Stream Header / Footer CRC32");
-	if (hf[6] != 0 || (hf[7] & 0xF0) || hf[6] != hf[20] || hf[7] != hf[21])
-		FAILD(XZAMD_OPTIONS_ERROR, "unsupported or inconsistent Stream Flags");
-	const int check = hf[7] & 0x0F;
-	/* a Check that cannot be verified is reported, not skipped (the reference: LZMA_UNSUPPORTED_CHECK) */
-	if (check != XZAMD_CHECK_NONE && check != XZAMD_CHECK_CRC32 && check != XZAMD_CHECK_CRC64 && check != XZAMD_CHECK_SHA256)
-		FAILD(XZAMD_UNSUPPORTED_CHECK, "Check id the device decoder cannot verify");
-	static const uint8_t check_sizes[16] = { 0, 4, 4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64 };
-	const uint32_t csz = check_sizes[check];
-	const uint64_t index_size = ((uint64_t)rd32(hf + 16) + 1) * 4;
-	if (index_size + 24 > xz_size)
-		FAILD(XZAMD_DATA_ERROR, "Backward Size");
-
-	/* Index */
-	index = (uint8_t *)malloc(index_size);
-	if (!index) FAILD(XZAMD_MEM_ERROR, "malloc");
-	HIPD(xzk_d2h(index, d_xz + xz_size - 12 - index_size, index_size, st) || xzk_sync(st), "d2h index");
-	if (index[0] != 0x00 || rd32(index + index_size - 4) != xzamd_crc32_host_(index, index_size - 4))
-		FAILD(XZAMD_DATA_ERROR, "Index indicator / CRC32");
-	size_t ip = 1;
-	uint64_t nb = 0;
-	if (vli_get(index, index_size - 4, &ip, &nb) || nb > (index_size / 2))
-		FAILD(XZAMD_DATA_ERROR, "Index record count");
-	hb = (xzamd_dec_block *)calloc(nb ? nb : 1, sizeof(*hb));
-	stored = (uint64_t *)calloc(nb ? nb : 1, 8);
-	h_crc = (uint64_t *)calloc(nb ? nb : 1, 8);
-	h_err = (uint32_t *)calloc(nb ? nb : 1, 4);
-	stored32 = (uint8_t *)calloc(nb ? nb : 1, 32);
-	if (!stored32) FAILD(XZAMD_MEM_ERROR, "malloc");
-	unit_first = (uint32_t *)calloc(nb + 1, 4);
-	hc = (xzamd_dec_chain *)calloc(nb ? nb : 1, sizeof(*hc));
-	tile_first = (uint32_t *)calloc(nb + 1, 4);
-	if (!hb || !stored || !h_crc || !h_err || !unit_first || !hc || !tile_first) FAILD(XZAMD_MEM_ERROR, "malloc");
-	uint64_t pos = 12, utotal = 0, max_usize = 0;
+	uint64_t utotal = 0, max_usize = 0;
+	if (nb == 0) return XZAMD_OK;
+	if (nb >= (1ull << 31)) return xzamd_ctx_fail_(c, XZAMD_OPTIONS_ERROR, "too many Blocks for the device decoder");
 	for (uint64_t b = 0; b < nb; ++b) {
-		uint64_t unpadded = 0, usize = 0;
-		if (vli_get(index, index_size - 4, &ip, &unpadded) || vli_get(index, index_size - 4, &ip, &usize)
-				|| unpadded < 5 + csz || unpadded > (1ull << 62))
-			FAILD(XZAMD_DATA_ERROR, "Index record");
-		/* Block Header */
-		uint8_t bh[1024];
-		if (pos + 8 > xz_size - 12 - index_size)
-			FAILD(XZAMD_DATA_ERROR, "Block beyond the Index");
-		const uint64_t avail_h = xz_size - 12 - index_size - pos;
-		HIPD(xzk_d2h(bh, d_xz + pos, avail_h < 64 ? avail_h : 64, st) || xzk_sync(st), "d2h block header");
-		if (bh[0] == 0)
-			FAILD(XZAMD_DATA_ERROR, "Index indicator where a Block Header was expected");
-		const uint32_t hs = ((uint32_t)bh[0] + 1) * 4;
-		if (hs > avail_h)
-			FAILD(XZAMD_DATA_ERROR, "Block Header beyond the Index");
-		if (hs > 64)
-			HIPD(xzk_d2h(bh, d_xz + pos, hs, st) || xzk_sync(st), "d2h block header");
-		if (rd32(bh + hs - 4) != xzamd_crc32_host_(bh, hs - 4))
-			FAILD(XZAMD_DATA_ERROR, "Block Header CRC32");
-		if (bh[1] & 0x3C)
-			FAILD(XZAMD_OPTIONS_ERROR, "reserved Block Flags");
-		size_t hp = 2;
-		uint64_t h_csize = UINT64_MAX, h_usize = UINT64_MAX;
-		if ((bh[1] & 0x40) && vli_get(bh, hs - 4, &hp, &h_csize)) FAILD(XZAMD_DATA_ERROR, "Block Header Compressed Size");
-		if ((bh[1] & 0x80) && vli_get(bh, hs - 4, &hp, &h_usize)) FAILD(XZAMD_DATA_ERROR, "Block Header Uncompressed Size");
-		/* Filter Flags, one after another as the reference reads them: the first error decides the code */
-		const uint32_t nfilt = (bh[1] & 3u) + 1;
-		uint32_t db = 0, lzma2_at = UINT32_MAX, nlzma2 = 0;
-		for (uint32_t i = 0; i < nfilt; ++i) {
-			uint64_t fid = 0, fps = 0;
-			if (vli_get(bh, hs - 4, &hp, &fid) || fid >= (1ull << 62) || vli_get(bh, hs - 4, &hp, &fps) || hs - 4 - hp < fps)
-				FAILD(XZAMD_DATA_ERROR, "Filter Flags");
-			const uint8_t *props = bh + hp;
-			uint32_t entry = 0;
-			if (fid == 0x21) {
-				if (fps != 1 || props[0] > 40) FAILD(XZAMD_OPTIONS_ERROR, "LZMA2 properties (dictionary size byte)");
-				db = props[0];
-				lzma2_at = i;
-				++nlzma2;
-			} else if (fid == 0x03) {
-				if (fps != 1) FAILD(XZAMD_OPTIONS_ERROR, "delta filter: size of properties");
-				entry = 3u | ((uint32_t)props[0] << 8);
-			} else if (fid >= 0x04 && fid <= 0x0B) {
-				if (fps != 0 && fps != 4) FAILD(XZAMD_OPTIONS_ERROR, "BCJ filter: size of properties");
-				if (fps == 4 && rd32(props) != 0)
-					FAILD(XZAMD_OPTIONS_ERROR, "BCJ filter with a non-zero start offset is not decoded on the device");
-				entry = (uint32_t)fid;
-			} else {
-				FAILD(XZAMD_OPTIONS_ERROR, "filter id the device decoder does not know");
-			}
-			if (entry && hc[b].n < XZAMD_DEC_FILTERS_MAX) hc[b].f[hc[b].n++] = entry;
-			hp += fps;
-		}
-		for (size_t q = hp; q < hs - 4; ++q)
-			if (bh[q] != 0) FAILD(XZAMD_OPTIONS_ERROR, "Block Header padding");
-		/* filter_common.c:250-294: LZMA2 ends the chain and stands nowhere else */
-		if (nlzma2 != 1 || lzma2_at != nfilt - 1)
-			FAILD(XZAMD_OPTIONS_ERROR, "filter chain: LZMA2 must be the last filter and only the last");
 		if (hc[b].n) { any_filtered = 1; if (hc[b].n > max_nf) max_nf = hc[b].n; } else any_plain = 1;
-		const uint32_t dict = db == 40 ? 0xFFFFFFFFu : ((2u | (db & 1u)) << (db / 2 + 11));
-		if (unpadded < hs + csz)
-			FAILD(XZAMD_DATA_ERROR, "Unpadded Size smaller than its header");
-		const uint64_t csize = unpadded - hs - csz;
-		if ((h_csize != UINT64_MAX && h_csize != csize) || (h_usize != UINT64_MAX && h_usize != usize) || csize == 0)
-			FAILD(XZAMD_DATA_ERROR, "Block Header sizes differ from the Index");
-		const uint64_t padded = (unpadded + 3) & ~3ull;
-		if (pos + padded > xz_size - 12 - index_size)
-			FAILD(XZAMD_DATA_ERROR, "Block beyond the Index");
-		hb[b].cpos = pos + hs;
-		hb[b].csize = csize;
-		hb[b].upos = utotal;
-		hb[b].usize = usize;
-		hb[b].dict_size = dict;
-		/* Block Padding must be zero; the stored Check */
-		uint8_t tail[3 + 64];
-		const uint32_t padn = (uint32_t)(padded - unpadded);
-		HIPD(xzk_d2h(tail, d_xz + pos + hs + csize, padn + csz, st) || xzk_sync(st), "d2h check");
-		for (uint32_t i = 0; i < padn; ++i)
-			if (tail[i] != 0) FAILD(XZAMD_DATA_ERROR, "Block Padding");
-		uint64_t sv = 0;
-		for (uint32_t i = 0; i < csz && i < 8; ++i) sv |= (uint64_t)tail[padn + i] << (8 * i);
-		stored[b] = sv;
-		if (csz == 32) memcpy(stored32 + 32 * b, tail + padn, 32);
-		pos += padded;
-		utotal += usize;
-		if (usize > max_usize) max_usize = usize;
-		if (usize >= (1ull << 31) || csize >= (1ull << 32))
-			FAILD(XZAMD_OPTIONS_ERROR, "Block too large for the device decoder");
+		utotal += hb[b].usize;
+		if (hb[b].usize > max_usize) max_usize = hb[b].usize;
 	}
-	for (; ip < index_size - 4; ++ip)
-		if (index[ip] != 0) FAILD(XZAMD_DATA_ERROR, "Index Padding");
-	if (pos != xz_size - 12 - index_size)
-		FAILD(XZAMD_DATA_ERROR, "Blocks do not end where the Index starts");
-	if (nblocks_out) *nblocks_out = nb;
-	*out_size = utotal;
-	if (utotal > out_cap)
-		FAILD(XZAMD_BUF_ERROR, "output buffer too small");
-	if (d_expected && expected_size != utotal)
-		FAILD(XZAMD_DATA_ERROR, "the Stream's uncompressed size differs from the size of the original given for verification");
-	if (nb == 0 || utotal == 0) {
-		if (nb != 0) {
-			/* Blocks of zero bytes still carry a chunk chain: decode it below */
-		} else goto done;
-	}
+	h_crc = (uint64_t *)calloc(nb, 8);
+	h_err = (uint32_t *)calloc(nb, 4);
+	unit_first = (uint32_t *)calloc(nb + 1, 4);
+	tile_first = (uint32_t *)calloc(nb + 1, 4);
+	if (!h_crc || !h_err || !unit_first || !tile_first) FAILD(XZAMD_MEM_ERROR, "malloc");
 
 	/* unit scan + decode */
 	{
 		const uint32_t nbk = (uint32_t)nb;
-		int split = d_expected != NULL;
+		int split = d_expected != NULL && j->allow_split;
 		uint32_t units_cap = split ? (uint32_t)(max_usize / 4096 + 8) : 1;
 		if ((uint64_t)units_cap * nb > (1ull << 27)) { split = 0; units_cap = 1; }
 		uint32_t waves = xzamd_ctx_wave_slots_(c);
@@ -287,6 +145,7 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 						HIPD(f == 4u ? xzk_x86_bcj(src, dst, (uint32_t)utotal, (uint32_t)bs0, nbk, st)
 								: xzk_prefilter(src, dst, (uint32_t)utotal, (uint32_t)bs0, nbk, f & 0xFFu, (f >> 8) + 1, st),
 								"forward filter of the verification decode");
+						launches_(j, 1);
 						count_(2);
 						src = dst;
 					}
@@ -301,7 +160,9 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 		HIPD(xzk_malloc(&d_units, (uint64_t)units_cap * nb * sizeof(xzamd_dec_unit)), "hipMalloc");
 		HIPD(xzk_h2d(d_blocks, hb, nb * sizeof(xzamd_dec_block), st), "h2d blocks");
 		HIPD(xzk_dec_scan(d_xz, (xzamd_dec_block *)d_blocks, nbk, (xzamd_dec_unit *)d_units, units_cap, split, st), "scan launch");
+		launches_(j, 1);
 		HIPD(xzk_d2h(hb, d_blocks, nb * sizeof(xzamd_dec_block), st) || xzk_sync(st), "d2h blocks");
+		reads_(j, 1);
 		uint32_t total_units = 0;
 		int overflow = 0;
 		for (uint64_t b = 0; b < nb; ++b) {
@@ -329,7 +190,9 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 		uint32_t *d_berr = (uint32_t *)((uint8_t *)d_misc + 4096);
 		HIPD(xzk_dec_units(d_xz, (const xzamd_dec_block *)d_blocks, nbk, (const xzamd_dec_unit *)d_units, units_cap,
 				(const uint32_t *)d_first, total_units, dec_out, hist, (uint16_t *)d_lit, waves, d_counter, d_berr, st), "decode launch");
+		launches_(j, 1);
 		HIPD(xzk_d2h(h_err, d_berr, 4 * nb, st) || xzk_sync(st), "decode");
+		reads_(j, 1);
 		for (uint64_t b = 0; b < nb; ++b)
 			if (h_err[b]) FAILD(XZAMD_DATA_ERROR, "LZMA2 data (range coder / distances / chunk sizes)");
 		if (any_filtered) {
@@ -365,60 +228,94 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 				/* tile_first is rewritten for the next stage: the copy must have left the host buffer first */
 				HIPD(xzk_h2d(d_tiles, tile_first, 4 * (nb + 1), st) || xzk_sync(st), "h2d tiles");
 				HIPD(xzk_dec_unfilter(&ua, (uint32_t)tiles, kinds, st), "inverse filter launch");
+				launches_(j, 1);
 				count_(1);
 			}
 		}
-		/* Block checks over the decoded bytes */
-		if (check == XZAMD_CHECK_CRC32 || check == XZAMD_CHECK_CRC64) {
-			const uint32_t strip = 4096;
-			int uniform = 1;
-			for (uint64_t b = 0; b + 1 < nb; ++b)
-				if (hb[b].usize != hb[0].usize) uniform = 0;
-			if (nb > 1 && hb[nb - 1].usize > hb[0].usize) uniform = 0;
-			const uint64_t bs0 = hb[0].usize ? hb[0].usize : 1;
-			const uint64_t spb = (max_usize + strip - 1) / strip + 1;
+		/* Block checks over the decoded bytes, one group of Blocks (= the Blocks of one Stream, one kind of Check) after
+		 * another; the results of all groups come back in one read per kind */
+		int any_crc = 0, any_sha = 0;
+		for (uint32_t g = 0; g < j->ngroups; ++g) {
+			if (j->groups[g].count == 0) continue;
+			if (j->groups[g].check == XZAMD_CHECK_CRC32 || j->groups[g].check == XZAMD_CHECK_CRC64) any_crc = 1;
+			if (j->groups[g].check == XZAMD_CHECK_SHA256) any_sha = 1;
+		}
+		if (any_crc) {
+			const uint64_t spb = (max_usize + 4096 - 1) / 4096 + 1;
 			HIPD(xzk_malloc(&d_strip, 8 * spb * nb + 64), "hipMalloc");
 			HIPD(xzk_malloc(&d_crc, 8 * nb + 64), "hipMalloc");
-			if (uniform && utotal < (1ull << 31)) {
-				HIPD(xzk_crc_blocks(d_out, (uint32_t)utotal, (uint32_t)bs0, nbk, strip, check == XZAMD_CHECK_CRC32,
-						(uint64_t *)d_strip, (uint64_t *)d_crc, st), "crc launch");
+		}
+		if (any_sha) {
+			HIPD(xzk_malloc(&d_sha, 32 * nb + 64), "hipMalloc");
+			h_sha = (uint8_t *)malloc(32 * nb);
+			if (!h_sha) FAILD(XZAMD_MEM_ERROR, "malloc");
+		}
+		for (uint32_t g = 0; g < j->ngroups; ++g) {
+			const int check = j->groups[g].check;
+			const uint64_t gn = j->groups[g].count;
+			const xzamd_dec_block *gb = hb + j->groups[g].first;
+			if (gn == 0 || check == XZAMD_CHECK_NONE) continue;
+			/* equally long Blocks but the last: one launch for the group, else one launch per Block */
+			int uniform = 1;
+			uint64_t gtotal = 0;
+			for (uint64_t b = 0; b < gn; ++b) gtotal += gb[b].usize;
+			for (uint64_t b = 0; b + 1 < gn; ++b)
+				if (gb[b].usize != gb[0].usize) uniform = 0;
+			if (gn > 1 && gb[gn - 1].usize > gb[0].usize) uniform = 0;
+			uint8_t *gout = d_out + gb[0].upos;
+			if (check == XZAMD_CHECK_CRC32 || check == XZAMD_CHECK_CRC64) {
+				const uint32_t strip = 4096;
+				const uint64_t bs0 = gb[0].usize ? gb[0].usize : 1;
+				uint64_t *g_crc = (uint64_t *)d_crc + j->groups[g].first;
+				if (uniform && gtotal < (1ull << 31)) {
+					HIPD(xzk_crc_blocks(gout, (uint32_t)gtotal, (uint32_t)bs0, (uint32_t)gn, strip, check == XZAMD_CHECK_CRC32,
+							(uint64_t *)d_strip, g_crc, st), "crc launch");
+					launches_(j, 1);
+				} else {
+					for (uint64_t b = 0; b < gn; ++b) {
+						if (gb[b].usize == 0) { HIPD(xzk_memset(g_crc + b, 0, 8, st), "memset"); continue; }
+						HIPD(xzk_crc_blocks(d_out + gb[b].upos, (uint32_t)gb[b].usize, (uint32_t)gb[b].usize, 1, strip,
+								check == XZAMD_CHECK_CRC32, (uint64_t *)d_strip, g_crc + b, st), "crc launch");
+						launches_(j, 1);
+					}
+				}
 			} else {
-				for (uint64_t b = 0; b < nb; ++b) {
-					if (hb[b].usize == 0) { HIPD(xzk_memset((uint8_t *)d_crc + 8 * b, 0, 8, st), "memset"); continue; }
-					HIPD(xzk_crc_blocks(d_out + hb[b].upos, (uint32_t)hb[b].usize, (uint32_t)hb[b].usize, 1, strip,
-							check == XZAMD_CHECK_CRC32, (uint64_t *)d_strip, (uint64_t *)d_crc + b, st), "crc launch");
+				/* check/sha256.c over the decoded bytes: one hash per Block (serial by nature) */
+				uint8_t *g_sha = (uint8_t *)d_sha + 32 * j->groups[g].first;
+				if (uniform && gtotal < (1ull << 31) && gb[0].usize) {
+					HIPD(xzk_sha256_blocks(gout, (uint32_t)gtotal, (uint32_t)gb[0].usize, (uint32_t)gn, g_sha, st), "sha256 launch");
+					launches_(j, 1);
+				} else {
+					for (uint64_t b = 0; b < gn; ++b) {
+						HIPD(xzk_sha256_blocks(d_out + gb[b].upos, (uint32_t)gb[b].usize, gb[b].usize ? (uint32_t)gb[b].usize : 1u, 1,
+								g_sha + 32 * b, st), "sha256 launch");
+						launches_(j, 1);
+					}
 				}
 			}
-			HIPD(xzk_d2h(h_crc, d_crc, 8 * nb, st) || xzk_sync(st), "d2h crc");
-			for (uint64_t b = 0; b < nb; ++b)
-				if (h_crc[b] != stored[b]) FAILD(XZAMD_DATA_ERROR, "Block Check mismatch");
 		}
-		if (check == XZAMD_CHECK_SHA256) {
-			/* check/sha256.c over the decoded bytes: one hash per Block (serial by nature); equally long Blocks in one
-			 * launch, else one launch each */
-			int uniform = 1;
-			for (uint64_t b = 0; b + 1 < nb; ++b)
-				if (hb[b].usize != hb[0].usize) uniform = 0;
-			if (nb > 1 && hb[nb - 1].usize > hb[0].usize) uniform = 0;
-			HIPD(xzk_malloc(&d_sha, 32 * nb + 64), "hipMalloc");
-			if (uniform && utotal < (1ull << 31) && hb[0].usize) {
-				HIPD(xzk_sha256_blocks(d_out, (uint32_t)utotal, (uint32_t)hb[0].usize, nbk, (uint8_t *)d_sha, st), "sha256 launch");
-			} else {
-				for (uint64_t b = 0; b < nb; ++b)
-					HIPD(xzk_sha256_blocks(d_out + hb[b].upos, (uint32_t)hb[b].usize, hb[b].usize ? (uint32_t)hb[b].usize : 1u, 1,
-							(uint8_t *)d_sha + 32 * b, st), "sha256 launch");
+		if (any_crc) { HIPD(xzk_d2h(h_crc, d_crc, 8 * nb, st), "d2h crc"); reads_(j, 1); }
+		if (any_sha) { HIPD(xzk_d2h(h_sha, d_sha, 32 * nb, st), "d2h sha256"); reads_(j, 1); }
+		if (any_crc || any_sha) HIPD(xzk_sync(st), "d2h checks");
+		for (uint32_t g = 0; g < j->ngroups; ++g) {
+			const int check = j->groups[g].check;
+			for (uint64_t b = j->groups[g].first; b < j->groups[g].first + j->groups[g].count; ++b) {
+				const uint8_t *sb = j->stored + XZAMD_HDR_CHECK_BYTES * b;
+				if (check == XZAMD_CHECK_CRC32 || check == XZAMD_CHECK_CRC64) {
+					uint64_t sv = 0;
+					for (uint32_t i = 0; i < (check == XZAMD_CHECK_CRC32 ? 4u : 8u); ++i) sv |= (uint64_t)sb[i] << (8 * i);
+					if (h_crc[b] != sv) FAILD(XZAMD_DATA_ERROR, "Block Check mismatch");
+				} else if (check == XZAMD_CHECK_SHA256) {
+					if (memcmp(h_sha + 32 * b, sb, 32) != 0) FAILD(XZAMD_DATA_ERROR, "Block Check mismatch (SHA-256)");
+				}
 			}
-			uint8_t *h_sha = (uint8_t *)malloc(32 * nb);
-			if (!h_sha) FAILD(XZAMD_MEM_ERROR, "malloc");
-			int bad = xzk_d2h(h_sha, d_sha, 32 * nb, st) || xzk_sync(st) ? -1 : memcmp(h_sha, stored32, 32 * nb) != 0;
-			free(h_sha);
-			if (bad < 0) FAILD(XZAMD_DEVICE_ERROR, "d2h sha256");
-			if (bad) FAILD(XZAMD_DATA_ERROR, "Block Check mismatch (SHA-256)");
 		}
 		if (d_expected) {
 			unsigned long long mm = 0;
 			HIPD(xzk_dec_compare(d_out, d_expected, utotal, d_mism, st), "compare launch");
+			launches_(j, 1);
 			HIPD(xzk_d2h(&mm, d_mism, 8, st) || xzk_sync(st), "d2h compare");
+			reads_(j, 1);
 			if (mismatches) *mismatches = mm;
 			if (mm) FAILD(XZAMD_DATA_ERROR, "decoded bytes differ from the original");
 		}
@@ -440,8 +337,141 @@ done:
 	if (d_filt) xzk_free(d_filt);
 	if (d_tsum) xzk_free(d_tsum);
 	if (d_tcarry) xzk_free(d_tcarry);
-	free(hc); free(tile_first);
-	free(stored32);
-	free(index); free(hb); free(stored); free(h_crc); free(h_err); free(unit_first);
+	free(tile_first); free(h_sha);
+	free(h_crc); free(h_err); free(unit_first);
 	return rc;
 }
+
+int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size, void *d_out_, uint64_t out_cap,
+		uint64_t *out_size, const void *d_expected_, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks_out,
+		void *stream)
+{
+	if (!c || !d_xz_ || !out_size || (!d_out_ && out_cap))
+		return XZAMD_PROG_ERROR;
+	const uint8_t *d_xz = (const uint8_t *)d_xz_;
+	uint8_t *d_out = (uint8_t *)d_out_;
+	const uint8_t *d_expected = (const uint8_t *)d_expected_;
+	void *st = stream ? stream : xzamd_ctx_stream_(c);
+	int rc = XZAMD_OK;
+	uint8_t *index = NULL;
+	xzamd_dec_block *hb = NULL;
+	uint8_t *stored32 = NULL;          /* the stored Check bytes of every Block */
+	xzamd_dec_chain *hc = NULL;        /* per Block: the filters in front of LZMA2 */
+	*out_size = 0;
+	if (mismatches) *mismatches = 0;
+	if (nblocks_out) *nblocks_out = 0;
+	if (xzk_set_device(xzamd_ctx_device(c)))
+		return xzamd_ctx_fail_(c, XZAMD_DEVICE_ERROR, "hipSetDevice");
+
+	/* Stream Header + Footer */
+	static const uint8_t magic[6] = { 0xFD, '7', 'z', 'X', 'Z', 0x00 };
+	uint8_t hf[24];
+	if (xz_size < 32 || (xz_size & 3))
+		FAILD(FORMAT_ERROR, "not an .xz Stream (size)");
+	HIPD(xzk_d2h(hf, d_xz, 12, st) || xzk_d2h(hf + 12, d_xz + xz_size - 12, 12, st) || xzk_sync(st), "d2h stream flags");
+	if (memcmp(hf, magic, 6) != 0 || hf[22] != 'Y' || hf[23] != 'Z')
+		FAILD(FORMAT_ERROR, "bad magic bytes");
+	if (rd32(hf + 8) != xzamd_crc32_host_(hf + 6, 2) || rd32(hf + 12) != xzamd_crc32_host_(hf + 16, 6))
+		FAILD(XZAMD_DATA_ERROR, "Stream Header / Footer CRC32");
+	if (hf[6] != 0 || (hf[7] & 0xF0) || hf[6] != hf[20] || hf[7] != hf[21])
+		FAILD(XZAMD_OPTIONS_ERROR, "unsupported or inconsistent Stream Flags");
+	const int check = hf[7] & 0x0F;
+	/* a Check that cannot be verified is reported, not skipped (the reference: LZMA_UNSUPPORTED_CHECK) */
+	if (check != XZAMD_CHECK_NONE && check != XZAMD_CHECK_CRC32 && check != XZAMD_CHECK_CRC64 && check != XZAMD_CHECK_SHA256)
+		FAILD(XZAMD_UNSUPPORTED_CHECK, "Check id the device decoder cannot verify");
+	static const uint8_t check_sizes[16] = { 0, 4, 4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64 };
+	const uint32_t csz = check_sizes[check];
+	const uint64_t index_size = ((uint64_t)rd32(hf + 16) + 1) * 4;
+	if (index_size + 24 > xz_size)
+		FAILD(XZAMD_DATA_ERROR, "Backward Size");
+
+	/* Index */
+	index = (uint8_t *)malloc(index_size);
+	if (!index) FAILD(XZAMD_MEM_ERROR, "malloc");
+	HIPD(xzk_d2h(index, d_xz + xz_size - 12 - index_size, index_size, st) || xzk_sync(st), "d2h index");
+	if (index[0] != 0x00 || rd32(index + index_size - 4) != xzamd_crc32_host_(index, index_size - 4))
+		FAILD(XZAMD_DATA_ERROR, "Index indicator / CRC32");
+	uint64_t ip = 1;
+	uint64_t nb = 0;
+	if (xzb_vli(index, index_size - 4, &ip, &nb) || nb > (index_size / 2))
+		FAILD(XZAMD_DATA_ERROR, "Index record count");
+	hb = (xzamd_dec_block *)calloc(nb ? nb : 1, sizeof(*hb));
+	stored32 = (uint8_t *)calloc(nb ? nb : 1, XZAMD_HDR_CHECK_BYTES);
+	hc = (xzamd_dec_chain *)calloc(nb ? nb : 1, sizeof(*hc));
+	if (!hb || !stored32 || !hc) FAILD(XZAMD_MEM_ERROR, "malloc");
+	uint64_t pos = 12, utotal = 0;
+	for (uint64_t b = 0; b < nb; ++b) {
+		uint64_t unpadded = 0, usize = 0;
+		if (xzb_vli(index, index_size - 4, &ip, &unpadded) || xzb_vli(index, index_size - 4, &ip, &usize)
+				|| unpadded < 5 + csz || unpadded > (1ull << 62))
+			FAILD(XZAMD_DATA_ERROR, "Index record");
+		/* Block Header */
+		uint8_t bh[1024];
+		if (pos + 8 > xz_size - 12 - index_size)
+			FAILD(XZAMD_DATA_ERROR, "Block beyond the Index");
+		const uint64_t avail_h = xz_size - 12 - index_size - pos;
+		HIPD(xzk_d2h(bh, d_xz + pos, avail_h < 64 ? avail_h : 64, st) || xzk_sync(st), "d2h block header");
+		if (bh[0] == 0)
+			FAILD(XZAMD_DATA_ERROR, "Index indicator where a Block Header was expected");
+		const uint32_t hs = ((uint32_t)bh[0] + 1) * 4;
+		if (hs > avail_h)
+			FAILD(XZAMD_DATA_ERROR, "Block Header beyond the Index");
+		if (hs > 64)
+			HIPD(xzk_d2h(bh, d_xz + pos, hs, st) || xzk_sync(st), "d2h block header");
+		uint64_t h_csize, h_usize;
+		uint32_t dict = 0, step = 0;
+		const uint32_t hcode = xzb_header(bh, hs, &h_csize, &h_usize, &hc[b], &dict, &step);
+		if (hcode) FAILD((int)hcode, xzamd_block_step_msg_(step));
+		if (unpadded < hs + csz)
+			FAILD(XZAMD_DATA_ERROR, "Unpadded Size smaller than its header");
+		const uint64_t csize = unpadded - hs - csz;
+		if ((h_csize != UINT64_MAX && h_csize != csize) || (h_usize != UINT64_MAX && h_usize != usize) || csize == 0)
+			FAILD(XZAMD_DATA_ERROR, "Block Header sizes differ from the Index");
+		const uint64_t padded = (unpadded + 3) & ~3ull;
+		if (pos + padded > xz_size - 12 - index_size)
+			FAILD(XZAMD_DATA_ERROR, "Block beyond the Index");
+		hb[b].cpos = pos + hs;
+		hb[b].csize = csize;
+		hb[b].upos = utotal;
+		hb[b].usize = usize;
+		hb[b].dict_size = dict;
+		/* Block Padding must be zero; the stored Check */
+		uint8_t tail[3 + 64];
+		const uint32_t padn = (uint32_t)(padded - unpadded);
+		HIPD(xzk_d2h(tail, d_xz + pos + hs + csize, padn + csz, st) || xzk_sync(st), "d2h check");
+		for (uint32_t i = 0; i < padn; ++i)
+			if (tail[i] != 0) FAILD(XZAMD_DATA_ERROR, "Block Padding");
+		memcpy(stored32 + XZAMD_HDR_CHECK_BYTES * b, tail + padn, csz);
+		pos += padded;
+		utotal += usize;
+		if (usize >= (1ull << 31) || csize >= (1ull << 32))
+			FAILD(XZAMD_OPTIONS_ERROR, "Block too large for the device decoder");
+	}
+	for (; ip < index_size - 4; ++ip)
+		if (index[ip] != 0) FAILD(XZAMD_DATA_ERROR, "Index Padding");
+	if (pos != xz_size - 12 - index_size)
+		FAILD(XZAMD_DATA_ERROR, "Blocks do not end where the Index starts");
+	if (nblocks_out) *nblocks_out = nb;
+	*out_size = utotal;
+	if (utotal > out_cap)
+		FAILD(XZAMD_BUF_ERROR, "output buffer too small");
+	if (d_expected && expected_size != utotal)
+		FAILD(XZAMD_DATA_ERROR, "the Stream's uncompressed size differs from the size of the original given for verification");
+	/* Blocks of zero bytes still carry a chunk chain: they are decoded like any other */
+	if (nb != 0) {
+		const xzamd_dec_group group = { 0, nb, check };
+		xzamd_dec_job job;
+		memset(&job, 0, sizeof(job));
+		job.d_xz = d_xz; job.d_out = d_out; job.d_expected = d_expected;
+		job.nb = nb; job.hb = hb; job.hc = hc; job.stored = stored32;
+		job.groups = &group; job.ngroups = 1;
+		job.allow_split = 1;
+		job.mismatches = mismatches;
+		rc = xzamd_dec_run_(c, st, &job);
+	}
+done:
+	xzk_sync(st);
+	free(hc); free(stored32); free(index); free(hb);
+	return rc;
+}
+

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/xz_amd.h"
+#include "kernels_api.h"
 
 uint32_t xzamd_crc32_host_(const uint8_t *p, size_t n);
 void *xzamd_ctx_stream_(xzamd_ctx *c);
@@ -21,6 +22,28 @@ int xzamd_stored_blocks_host_(const uint8_t *in, uint64_t n, uint64_t block_size
 /* test instrumentation of the device decoder: temporaries allocated for inverse filters, inverse-stage calls, forward-filter
  * launches of verification decodes (process-wide counts) */
 void xzamd_debug_decode_counters_(uint64_t out[3]);
+
+/* The device part of a decode (xzamd_decode.c), shared by the single-Stream entry and the file entries (xzamd_file.c). */
+typedef struct {
+	uint64_t first, count;          /* Blocks [first, first + count) of the job ... */
+	int check;                      /* ... carry this Check (the Blocks of one Stream) */
+} xzamd_dec_group;
+typedef struct {
+	const uint8_t *d_xz;
+	uint8_t *d_out;                 /* Block b is written at d_out + hb[b].upos */
+	const uint8_t *d_expected;      /* the original of all of d_out, or NULL */
+	uint64_t nb;
+	xzamd_dec_block *hb;            /* parsed Blocks (xzb_block); nunits / error are scratch */
+	const xzamd_dec_chain *hc;
+	const uint8_t *stored;          /* XZAMD_HDR_CHECK_BYTES per Block: the stored Check */
+	const xzamd_dec_group *groups;  /* in Block order, every Block in exactly one group */
+	uint32_t ngroups;
+	int allow_split;                /* with d_expected: span-parallel units (else unit = Block; compared either way) */
+	uint64_t *mismatches;           /* optional */
+	uint64_t *counts;               /* optional: [0] += device-to-host reads, [1] += kernel-launch calls */
+} xzamd_dec_job;
+int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j);
+const char *xzamd_block_step_msg_(uint32_t step);
 
 double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt);   /* device work buffers per input byte of a batch */
 #endif

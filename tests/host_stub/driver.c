@@ -1,5 +1,5 @@
-/* driver.c -- TEST INFRASTRUCTURE ONLY: drives the product's plain-C host layer (xzamd_stream.c + xzamd_host.c over
- * the CPU stand-in stub_xzk.c) through the liblzma entry points the way a client does, under sanitizers.
+/* driver.c -- TEST INFRASTRUCTURE ONLY: drives the product's plain-C host layer (xzamd_stream.c + xzamd_host.c, xzamd_frame.c,
+ * xzamd_options.c over the CPU stand-in stub_xzk.c) through the liblzma entry points the way a client does, under sanitizers.
  * usage: driver OUTDIR   -> writes OUTDIR/caseN.in / caseN.xz; exit code 0 when every call behaved. */
 #include "../../include/xz_amd.h"
 #include "../../include/xz_amd_lzma.h"

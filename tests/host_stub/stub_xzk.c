@@ -1,6 +1,6 @@
 /* stub_xzk.c -- TEST INFRASTRUCTURE ONLY: a CPU stand-in for the kernels_api.h layer (the .hip units of xz_amd/csrc), so that the
- * plain-C host code of the product (xzamd_host.c: batch geometry, span plan bookkeeping, ordered layout, stored-Block
- * fallback, framing; xzamd_stream.c: the lzma_code state machine, worker threads, ordered job queue, timeouts) can
+ * plain-C host code of the product (xzamd_host.c: batch geometry, span plan bookkeeping, ordered layout; xzamd_frame.c:
+ * framing, stored-Block fallback; xzamd_options.c: presets, option checks; xzamd_stream.c: the lzma_code state machine, worker threads, ordered job queue, timeouts) can
  * run under AddressSanitizer / UndefinedBehaviorSanitizer / ThreadSanitizer on a box without a GPU (SURVEY.md 5:
  * sanitizer builds, race detection).  It is linked ONLY into tests/host_stub's test binary, never into
  * libxz_amd.so.  "Device" memory is host memory, streams are synchronous, the span kernel emits LZMA2 UNCOMPRESSED

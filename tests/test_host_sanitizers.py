@@ -1,8 +1,8 @@
 """Sanitizer builds of the plain-C host layer (ASan/UBSan builds, race detection).
 
-xzamd_stream.c (lzma_code state machine, worker threads, ordered job queue) and xzamd_host.c (batch geometry, span
-plan bookkeeping, layout, stored Blocks, framing) are compiled with -fsanitize=address,undefined and, separately,
--fsanitize=thread, on top of tests/host_stub/stub_xzk.c -- a CPU stand-in for the kernel layer whose "span kernel"
+xzamd_stream.c (lzma_code state machine, worker threads, ordered job queue), xzamd_host.c (batch geometry, span
+plan bookkeeping, layout), xzamd_frame.c (framing, stored Blocks) and xzamd_options.c (presets, option checks) are
+compiled with -fsanitize=address,undefined and, separately, -fsanitize=thread, on top of tests/host_stub/stub_xzk.c -- a CPU stand-in for the kernel layer whose "span kernel"
 emits LZMA2 uncompressed chunks -- and driven through the liblzma entry points by tests/host_stub/driver.c.  The
 Streams the host code frames must decode bit-exactly through the oracle decoder and the real reference decoder.
 Test infrastructure only: nothing here is linked into libxz_amd.so."""
@@ -15,7 +15,7 @@ import pytest
 import _oracle as o
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = [os.path.join(ROOT, "xz_amd", "csrc", f) for f in ("xzamd_stream.c", "xzamd_host.c", "corpus.c")] + \
+SRC = [os.path.join(ROOT, "xz_amd", "csrc", f) for f in ("xzamd_stream.c", "xzamd_host.c", "xzamd_frame.c", "xzamd_options.c", "corpus.c")] + \
       [os.path.join(ROOT, "tests", "host_stub", f) for f in ("stub_xzk.c", "driver.c")]
 
 

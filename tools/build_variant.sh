@@ -10,6 +10,7 @@ for u in *.hip; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -std=c++17 -fPIC -fno-strict-aliasing $FLAGS -c $u -o /tmp/${u%.hip}_$NAME.o
   OBJS="$OBJS /tmp/${u%.hip}_$NAME.o"
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libxz_amd_$NAME.so $OBJS xzamd_host.o xzamd_stream.o xzamd_decode.o corpus.o \
+# the plain-C objects: whatever the Makefile links into the product
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libxz_amd_$NAME.so $OBJS $(make -s print-host-objs) \
   -Wl,-Bsymbolic -Wl,--version-script=libxz_amd.map -Wl,-soname,libxz_amd.so -lpthread
 ls -la ../libxz_amd_$NAME.so

@@ -1,5 +1,5 @@
-/* kernels_api.h -- internal ABI between the plain-C host layer (xzamd_host.c) and the HIP
- * units (lzma_build.hip, lzma_find.hip, lzma_kernels.hip, lzma_filters.hip, hip_shims.hip,
+/* kernels_api.h -- internal ABI between the plain-C host layer (xzamd_host.c, xzamd_stream.c and the decoder units;
+ * xzamd_frame.c and xzamd_options.c call nothing of it) and the HIP units (lzma_build.hip, lzma_find.hip, lzma_kernels.hip, lzma_filters.hip, hip_shims.hip,
  * lzma_decode.hip).  Plain C types only; not part of the public C ABI (that is include/xz_amd.h). */
 #ifndef XZAMD_KERNELS_API_H
 #define XZAMD_KERNELS_API_H

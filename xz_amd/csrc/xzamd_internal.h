@@ -46,4 +46,27 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j);
 const char *xzamd_block_step_msg_(uint32_t step);
 
 double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt);   /* device work buffers per input byte of a batch */
+
+/* Shared by the host units only.  The version script exports every xzamd_* name; these stay inside the library. */
+#define XZAMD_HIDDEN __attribute__((visibility("hidden")))
+
+/* xzamd_frame.c: the container pieces the batch encoder lays out itself */
+XZAMD_HIDDEN void xzamd_le32_(uint8_t *p, uint32_t v);
+XZAMD_HIDDEN uint32_t xzamd_check_bytes_(int check);               /* 0xFFFFFFFF: not a Check this library writes */
+XZAMD_HIDDEN uint8_t xzamd_dict_size_byte_(uint32_t dict_size);
+XZAMD_HIDDEN uint32_t xzamd_prefilter_list_(const xzamd_lzma_options *opt, uint32_t pre[XZAMD_PREFILTERS_MAX]);
+XZAMD_HIDDEN int xzamd_prefilter_valid_(uint32_t pre);
+XZAMD_HIDDEN uint32_t xzamd_block_header_size_(uint64_t csize, uint64_t usize, const xzamd_lzma_options *opt);
+XZAMD_HIDDEN void xzamd_block_header_put_(uint8_t *out, uint32_t hs, uint64_t csize, uint64_t usize, uint8_t dict_byte,
+		const xzamd_lzma_options *opt);
+
+/* xzamd_options.c: the encode mode of an option set */
+typedef struct {
+	int adaptive;            /* cost-balanced spans, cut on the device */
+	int two;                 /* two-phase: parse pieces record symbols, encode spans code them */
+	int list_packed;         /* match lists without the separate lengths */
+	uint32_t model_slots;    /* probabilities of the model, padded */
+	uint32_t span_default;   /* span size when the options name none */
+} xzamd_mode;
+XZAMD_HIDDEN xzamd_mode xzamd_mode_of_(const xzamd_lzma_options *opt);
 #endif

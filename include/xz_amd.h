@@ -21,6 +21,8 @@
  *        lzma_stream_encoder_mt()   stream_encoder_mt.c:1196
  *        lzma_code()/lzma_end()     common/common.c:203,379
  *        lzma_get_progress()        common/common.c:406
+ *        lzma_stream_encoder()      common/stream_encoder.c:341   (one Block per Stream, coded in segments:
+ *        lzma_easy_encoder()        common/easy_encoder.c          XZAMD_F_SEGMENTS below)
  */
 #ifndef XZ_AMD_H
 #define XZ_AMD_H
@@ -214,6 +216,15 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
  * block_size 0 = xzamd_mt_block_size(opt). check = XZAMD_CHECK_*.
  * Returns XZAMD_OK or an error code. */
 #define XZAMD_F_BLOCKS_ONLY 1u
+/* XZAMD_F_SEGMENTS (implies XZAMD_F_BLOCKS_ONLY): every block_size bytes of the input are a SEGMENT of one larger Block
+ * that the caller frames (the single-Block Stream of lzma_stream_encoder).  Per segment only its LZMA2
+ * chunk chain is written -- the bytes between the Block Header and the end marker of the Block the MT layout would make
+ * of it: no header, no 0x00 end marker, no padding, no Check.  Every chain starts with a dictionary reset, so the
+ * chains of consecutive segments followed by one 0x00 are one valid LZMA2 stream.  binfo[i] then carries:
+ * total_size = length of the chain, uncompressed_size, out_offset, and unpadded_size = the segment's Check value
+ * (CRC32 zero-extended / CRC64; 0 for XZAMD_CHECK_NONE) for xzamd_crc32_combine / xzamd_crc64_combine.
+ * Chain {LZMA2} and Checks none / CRC32 / CRC64 only (else XZAMD_OPTIONS_ERROR). */
+#define XZAMD_F_SEGMENTS 2u
 
 typedef struct {
 	uint64_t unpadded_size;      /* Index record field 1 (block_util.c:45-76) */
@@ -235,7 +246,10 @@ int xzamd_stream_encode_device(xzamd_ctx *ctx,
  * {up to three of: delta (0x03) | x86, PowerPC, IA-64, ARM, ARM-Thumb, SPARC, ARM64, RISC-V BCJ (0x04 .. 0x0B), LZMA2};
  * declined with XZAMD_OPTIONS_ERROR: a BCJ start offset other than 0, any other filter id, any chain the reference's
  * lzma_validate_chain refuses.  A Stream with a filtered Block needs one or two temporaries of the uncompressed size.
- * Checks none / CRC32 / CRC64 / SHA-256 are verified, any other Check id is XZAMD_UNSUPPORTED_CHECK.  Blocks decode in parallel, one wavefront each.  With d_expected (the original
+ * Checks none / CRC32 / CRC64 / SHA-256 are verified, any other Check id is XZAMD_UNSUPPORTED_CHECK.  Blocks decode in parallel; inside a
+ * Block a decode unit (one wavefront) starts at every LZMA2 chunk that resets the dictionary (control 0x01 or >= 0xE0): nothing in front
+ * of it can be referenced, so a Block of many segments (lzma_stream_encoder's) decodes segment-parallel and a Block with one reset (the MT
+ * encoders') is one unit; at most usize / 4096 + 8 units per Block, further resets stay inside the last unit.  With d_expected (the original
  * data, device memory, expected_size bytes: a Stream of another uncompressed size is XZAMD_DATA_ERROR) it is a VERIFICATION decode: every chunk chain that starts with a state
  * reset + properties (our spans) is its own unit, history is read from d_expected, and the decoded bytes are
  * compared with it afterwards (*mismatches).  For a filtered Stream the history is the filtered original (made with the
@@ -314,6 +328,12 @@ int xzamd_file_decode_range_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz
 uint64_t xzamd_frame_header(uint8_t *out, int check);
 uint64_t xzamd_frame_index_footer(uint8_t *out, uint64_t out_cap, int check,
 		const uint64_t *unpadded, const uint64_t *uncompressed, uint64_t nblocks);
+
+/* CRC of the concatenation A || B from crc(A), crc(B) and the length of B: crc(A) is advanced over len_b zero bytes
+ * (multiplication by x^(8 len_b) in GF(2)[x] modulo the polynomial, by squaring) and crc(B) is added.  CRC32 = the
+ * IEEE 802.3 polynomial (zlib.crc32, check/crc32_fast.c), CRC64 = ECMA-182 as liblzma writes it (check/crc64_fast.c). */
+uint32_t xzamd_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+uint64_t xzamd_crc64_combine(uint64_t crc_a, uint64_t crc_b, uint64_t len_b);
 
 /* Debug hook for the parity tests: when set, the next encode records every
  * LZMA symbol (span, pos, back, len as 4 x u32) into a device buffer of

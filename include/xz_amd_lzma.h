@@ -1,7 +1,7 @@
 /*
  * xz_amd_lzma.h -- the slice of liblzma's public C ABI that libxz_amd.so
- * implements as a drop-in: the multi-threaded .xz Stream encoder entry points
- * and the generic lzma_code()/lzma_end() pair that drive it.
+ * implements as a drop-in: the multi-threaded and the single-threaded .xz Stream
+ * encoder entry points and the generic lzma_code()/lzma_end() pair that drive them.
  *
  * A client compiled against the real <lzma.h> links against libxz_amd.so
  * unchanged for these symbols (same names, argument meaning, return codes and
@@ -14,6 +14,8 @@
  *   lzma_code                        replaces common/common.c:203 (for streams made here)
  *   lzma_end                         replaces common/common.c:379
  *   lzma_get_progress                replaces common/common.c:406
+ *   lzma_stream_encoder              replaces common/stream_encoder.c:341
+ *   lzma_easy_encoder                replaces common/easy_encoder.c
  *
  * Behavioural notes (INTEGRATION.md has the full list):
  *   - lzma_mt.threads caps the number of worker threads = GPUs used (one worker per visible GPU);
@@ -21,7 +23,8 @@
  *     that returns because of it returns LZMA_OK like the reference (stream_encoder_mt.c:667-713);
  *     LZMA_FULL_BARRIER returns once the input has been handed over (:803-807).
  *   - filters: {LZMA2} and {up to three BCJ (any of the eight) | delta filters, LZMA2} chains; LZMA_SYNC_FLUSH is unsupported
- *     exactly like the reference MT encoder (stream_encoder_mt.c:1201-1205).
+ *     exactly like the reference MT encoder (stream_encoder_mt.c:1201-1205); lzma_stream_encoder / lzma_easy_encoder
+ *     take it (see their declaration below).
  *   - check: LZMA_CHECK_NONE, LZMA_CHECK_CRC32, LZMA_CHECK_CRC64 (the xz default) and
  *     LZMA_CHECK_SHA256; others return LZMA_UNSUPPORTED_CHECK.
  */
@@ -163,6 +166,17 @@ void lzma_get_progress(lzma_stream *strm, uint64_t *progress_in, uint64_t *progr
 uint64_t lzma_mt_block_size(const lzma_filter *filters);
 uint32_t lzma_cputhreads(void);
 lzma_ret lzma_filters_update(lzma_stream *strm, const lzma_filter *filters);
+
+/* The single-threaded .xz Stream encoder (common/stream_encoder.c:341, common/easy_encoder.c), driven through the same
+ * lzma_code / lzma_end / lzma_get_progress.  Layout of the reference: one Block per Stream (one more per LZMA_FULL_FLUSH /
+ * LZMA_FULL_BARRIER), Block Header without Compressed / Uncompressed Size.  The Block's LZMA2 data is made of segments of
+ * lzma_mt_block_size(filters) bytes (XZAMD_SEGMENT_KIB overrides), each coded on the device like a Block of the MT
+ * encoder and starting with a dictionary reset; LZMA_SYNC_FLUSH ends the current segment where the input stands, hands
+ * out every byte up to there and returns LZMA_STREAM_END.  The output depends on the input, the options and the
+ * positions of the flushes only.  Declined with LZMA_OPTIONS_ERROR at init: every chain but {LZMA2}, LZMA_CHECK_SHA256,
+ * and what lzma_stream_encoder_mt declines. */
+lzma_ret lzma_stream_encoder(lzma_stream *strm, const lzma_filter *filters, lzma_check check);
+lzma_ret lzma_easy_encoder(lzma_stream *strm, uint32_t preset, lzma_check check);
 
 /* One-shot buffer API (common/stream_buffer_encoder.c:43-141, common/easy_buffer_encoder.c:16-27), same
  * return codes (LZMA_BUF_ERROR and *out_pos untouched if the output does not fit).  Like the reference the

@@ -18,6 +18,7 @@ SPAN_WHOLE_BLOCK = 0xFFFFFFFF
 SPAN_DEFAULT = 0
 SPAN_AUTO = 1
 F_BLOCKS_ONLY = 1
+F_SEGMENTS = 2
 BCJ_X86 = 4
 BCJ_ARM64 = 0x0A
 BCJ_RISCV = 0x0B
@@ -121,6 +122,11 @@ def lib():
                                                          C.POINTER(C.c_uint64), C.c_void_p]
             l.xzamd_debug_file_counters_.restype = None
             l.xzamd_debug_file_counters_.argtypes = [C.POINTER(C.c_uint64)]
+        if hasattr(l, "xzamd_crc32_combine"):           # (an older library lacks the single-Block encoder)
+            l.xzamd_crc32_combine.restype = C.c_uint32
+            l.xzamd_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+            l.xzamd_crc64_combine.restype = C.c_uint64
+            l.xzamd_crc64_combine.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
         l.xzamd_debug_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         l.xzamd_trace_enable.argtypes = [C.c_void_p, C.c_uint32]
         l.xzamd_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -205,6 +211,17 @@ def _file_index(call, what, detail):
     if rc != 0:
         raise XzAmdError(f"{what} failed ({rc})" + detail(), rc)
     return ([_stream_dict(s) for s in streams[: ns.value]], [_block_dict(b) for b in blocks[: nb.value]], usz.value)
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """CRC32 of A || B from crc32(A), crc32(B) and len(B) (xzamd_crc32_combine): how the single-Block encoder makes the
+    Check of a Block from the Checks of its segments."""
+    return lib().xzamd_crc32_combine(crc_a, crc_b, len_b)
+
+
+def crc64_combine(crc_a, crc_b, len_b):
+    """The same for the CRC64 of the .xz format (xzamd_crc64_combine)."""
+    return lib().xzamd_crc64_combine(crc_a, crc_b, len_b)
 
 
 def file_index(xz_bytes):
@@ -370,6 +387,16 @@ class Encoder:
         filters, inverse-stage calls, forward-filter launches of verification decodes)."""
         a = (C.c_uint64 * 3)()
         f = lib().xzamd_debug_decode_counters_        # bound here: an older library (XZ_AMD_LIB, A/B runs) lacks it
+        f.restype, f.argtypes = None, [C.POINTER(C.c_uint64)]
+        f(a)
+        return tuple(a)
+
+    @staticmethod
+    def debug_decode_units():
+        """The last decode launch of the process (test instrumentation): (units, Blocks, split mode of the unit scan: 0 = a
+        unit per Block, 1 = verification units at state resets, 2 = plain units at dictionary resets)."""
+        a = (C.c_uint64 * 3)()
+        f = lib().xzamd_debug_decode_units_
         f.restype, f.argtypes = None, [C.POINTER(C.c_uint64)]
         f(a)
         return tuple(a)

@@ -225,11 +225,16 @@ typedef struct {
 	uint32_t dbase;      /* Block offset of the last dictionary reset at or before the unit */
 } xzamd_dec_unit;
 
+/* split: 0 = one unit per Block; 1 = a unit at every chunk that resets the state and carries the properties (verification
+ * decode: history is the original; a full unit table is error 11); 2 = a unit at every chunk that resets the dictionary
+ * (plain decode; once the table is full, further resets stay inside the last unit) */
 int xzk_dec_scan(const uint8_t *d_xz, xzamd_dec_block *d_blocks, uint32_t nblocks, xzamd_dec_unit *d_units,
 		uint32_t units_cap, int split, void *stream);
+/* d_expected: one wavefront per unit, history read from it.  Else per_unit != 0: one wavefront per unit (units that start
+ * at dictionary resets, split 2), history = d_out; per_unit == 0: one wavefront per Block. */
 int xzk_dec_units(const uint8_t *d_xz, const xzamd_dec_block *d_blocks, uint32_t nblocks, const xzamd_dec_unit *d_units,
 		uint32_t units_cap, const uint32_t *d_unit_first, uint32_t total_units, uint8_t *d_out, const uint8_t *d_expected,
-		uint16_t *d_lit_pool, uint32_t waves, uint32_t *d_counter, uint32_t *d_block_err, void *stream);
+		uint16_t *d_lit_pool, uint32_t waves, uint32_t *d_counter, uint32_t *d_block_err, int per_unit, void *stream);
 int xzk_dec_compare(const uint8_t *a, const uint8_t *b, uint64_t n, unsigned long long *d_mismatches, void *stream);
 
 /* ---- inverse filters of the Block decoder (lzma_decode.hip) ----

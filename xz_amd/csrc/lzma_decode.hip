@@ -14,6 +14,10 @@
 //                            original instead of from a neighbour's unfinished output.  The decoded bytes
 //                            are written out and compared with the original afterwards, so a stream that
 //                            only decodes correctly "by luck of the oracle" cannot pass.
+//   * plain decode:          every chunk that resets the DICTIONARY (control 0x01 or >= 0xE0) begins an
+//                            independent unit: nothing in front of it can be referenced (a distance that
+//                            reaches there is DEC_BAD_DISTANCE), so the unit reads only what it wrote itself.
+//                            A Block of one dictionary reset -- everything the MT encoders write -- is one unit.
 // k_dec_scan walks the chunk headers of every Block (grammar checks of lzma2_decoder.c:67-127) and lists
 // the unit starts; k_dec_units decodes.
 #include <hip/hip_runtime.h>
@@ -63,7 +67,8 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
                 need_props = false;
             }
             if (need_props) { err = DEC_NEED_PROPS; break; }
-            if (ctl >= 0xC0 && split) starts_unit = true;      // carries the properties and resets the state: self-contained
+            if (ctl >= 0xC0 && split == 1) starts_unit = true; // carries the properties and resets the state: self-contained
+            if (ctl >= 0xE0 && split == 2) starts_unit = true; // dictionary reset: nothing in front of it is referenced
         } else if (ctl == 0x01 || ctl == 0x02) {
             if (c + 3 > B.csize) { err = DEC_TRUNCATED; break; }
             if (ctl == 0x01) { need_dict_reset = false; need_props = true; dbase = u; }     // lzma2_decoder.c:121-127
@@ -71,8 +76,12 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
             us = (((uint64_t)p[c + 1] << 8) | p[c + 2]) + 1;
             cs = us;
             hs = 3;
+            if (ctl == 0x01 && split == 2) starts_unit = true;
         } else { err = DEC_BAD_CONTROL; break; }
         if (c + hs + cs > B.csize || u + us > B.usize) { err = DEC_SIZE_MISMATCH; break; }
+        // split 2: the unit count is data.  A full table is no error there: further resets stay inside the last unit
+        // (decode_units follows a dictionary reset in the middle of a unit)
+        if (starts_unit && split == 2 && nunits == units_cap) starts_unit = false;
         if (starts_unit) {
             if (nunits == units_cap) { err = DEC_UNIT_OVERFLOW; break; }
             U[nunits].cpos = B.cpos + c;
@@ -349,25 +358,33 @@ __device__ __noinline__ void decode_units(const uint8_t* __restrict__ xz, const 
             c += hs + cs;
         }
     }
-    if (err != DEC_OK && lane == 0) atomicCAS(err_out, 0u, err);
+    // plain decode: units of a Block may run side by side, the Block's code is that of its lowest-numbered failing unit
+    // (code in the low byte; the host reads "not zero")
+    if (err != DEC_OK && lane == 0) {
+        if (plain) atomicMax(err_out, ((0xFFFFFFu - min(u0, 0xFFFFFEu)) << 8) | err);
+        else atomicCAS(err_out, 0u, err);
+    }
 }
 
-// mode 0: one wavefront per Block; mode 1 (verification): one wavefront per unit, history = original data
+// expected == nullptr, per_unit == 0: one wavefront per Block; verification (expected): one wavefront per unit of the
+// flattened list, history = original data; plain with per_unit (units start at dictionary resets): one wavefront per
+// unit, history = the output itself -- dbase of such a unit is its own start, so no unit reads what another writes
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_dec_units(const uint8_t* __restrict__ xz, const xzamd_dec_block* __restrict__ blocks,
         uint32_t nblocks, const xzamd_dec_unit* __restrict__ units, uint32_t units_cap, const uint32_t* __restrict__ unit_first,
         uint32_t total_units, uint8_t* __restrict__ out, const uint8_t* __restrict__ expected,
-        uint16_t* __restrict__ lit_pool, uint32_t* __restrict__ counter, uint32_t* __restrict__ block_err)
+        uint16_t* __restrict__ lit_pool, uint32_t* __restrict__ counter, uint32_t* __restrict__ block_err, int per_unit)
 {
     __shared__ uint16_t probs[D_TOTAL + 2];
     uint16_t* lit = lit_pool + (uint64_t)blockIdx.x * (0x300u << 4);
-    const uint32_t total = expected ? total_units : nblocks;
+    const bool flat = expected != nullptr || per_unit != 0;       // kernel arguments: wave-uniform
+    const uint32_t total = flat ? total_units : nblocks;
     for (;;) {
         uint32_t w = 0;
         if (threadIdx.x == 0) w = atomicAdd(counter, 1u);
         w = uni(w);
         if (w >= total) break;
         uint32_t bi = w, k0 = 0, k1 = 0;
-        if (expected) {
+        if (flat) {
             // unit w of the flattened list: find its Block (unit_first = exclusive prefix sum of nunits)
             uint32_t lo = 0, hi = nblocks;
             while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (unit_first[mid] <= w) lo = mid; else hi = mid; }
@@ -886,13 +903,13 @@ int xzk_dec_headers(const uint8_t* d_xz, uint64_t xz_size, const xzamd_hdr_rec* 
 
 int xzk_dec_units(const uint8_t* d_xz, const xzamd_dec_block* d_blocks, uint32_t nblocks, const xzamd_dec_unit* d_units,
         uint32_t units_cap, const uint32_t* d_unit_first, uint32_t total_units, uint8_t* d_out, const uint8_t* d_expected,
-        uint16_t* d_lit_pool, uint32_t waves, uint32_t* d_counter, uint32_t* d_block_err, void* stream_)
+        uint16_t* d_lit_pool, uint32_t waves, uint32_t* d_counter, uint32_t* d_block_err, int per_unit, void* stream_)
 {
-    const uint32_t total = d_expected ? total_units : nblocks;
+    const uint32_t total = (d_expected || per_unit) ? total_units : nblocks;
     if (total == 0) return 0;
     const uint32_t grid = waves < total ? waves : total;
     hipLaunchKernelGGL(k_dec_units, dim3(grid), dim3(64), 0, (hipStream_t)stream_, d_xz, d_blocks, nblocks, d_units, units_cap,
-            d_unit_first, total_units, d_out, d_expected, d_lit_pool, d_counter, d_block_err);
+            d_unit_first, total_units, d_out, d_expected, d_lit_pool, d_counter, d_block_err, per_unit);
     return (int)hipGetLastError();
 }
 

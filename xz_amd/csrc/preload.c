@@ -8,10 +8,12 @@
  * stream (SURVEY.md 8b "What calls it", option 2):
  *   lzma_stream_encoder_mt  -> libxz_amd.so (falls back to the real liblzma if there is no GPU or the
  *                              options are outside the device path)
+ *   lzma_stream_encoder, lzma_easy_encoder
+ *                           -> the same routing for the single-threaded encoder (`xz -T1`, Python's lzma, libarchive):
+ *                              libxz_amd.so when its init returns LZMA_OK, else the real liblzma
  *   lzma_code / lzma_end / lzma_get_progress / lzma_filters_update
  *                           -> libxz_amd.so for streams it created (tagged lzma_internal), the real
- *                              liblzma (dlsym RTLD_NEXT) for all others (decoders, single-threaded
- *                              encoder, ...)
+ *                              liblzma (dlsym RTLD_NEXT) for all others (decoders, raw and Block encoders, ...)
  * libxz_amd.so is opened RTLD_LOCAL so its own lzma_* exports never enter the global scope.
  * Environment: XZ_AMD_DISABLE=1 bypasses the GPU, XZ_AMD_VERBOSE=1 reports the routing on stderr.
  */
@@ -29,6 +31,8 @@
 #define XZAMD_MAGIC 0x585A414D44474655ull
 
 typedef lzma_ret (*enc_mt_fn)(lzma_stream *, const lzma_mt *);
+typedef lzma_ret (*enc_st_fn)(lzma_stream *, const lzma_filter *, lzma_check);
+typedef lzma_ret (*enc_easy_fn)(lzma_stream *, uint32_t, lzma_check);
 typedef lzma_ret (*code_fn)(lzma_stream *, lzma_action);
 typedef void (*end_fn)(lzma_stream *);
 typedef void (*progress_fn)(lzma_stream *, uint64_t *, uint64_t *);
@@ -38,6 +42,8 @@ static struct {
 	int tried;
 	void *h;
 	enc_mt_fn enc_mt;
+	enc_st_fn enc_st;           /* NULL with an older libxz_amd.so (XZ_AMD_LIB): those streams stay on liblzma */
+	enc_easy_fn enc_easy;
 	code_fn code;
 	end_fn end;
 	progress_fn progress;
@@ -74,6 +80,8 @@ static void gpu_load(void)
 		return;
 	}
 	gpu.enc_mt = (enc_mt_fn)dlsym(h, "lzma_stream_encoder_mt");
+	gpu.enc_st = (enc_st_fn)dlsym(h, "lzma_stream_encoder");
+	gpu.enc_easy = (enc_easy_fn)dlsym(h, "lzma_easy_encoder");
 	gpu.code = (code_fn)dlsym(h, "lzma_code");
 	gpu.end = (end_fn)dlsym(h, "lzma_end");
 	gpu.progress = (progress_fn)dlsym(h, "lzma_get_progress");
@@ -94,6 +102,26 @@ static int is_ours(const lzma_stream *strm)
 	return tag == XZAMD_MAGIC;
 }
 
+/* re-initialising a stream that belongs to the real library: let it free its coder */
+static void end_foreign(lzma_stream *strm)
+{
+	if (strm && strm->internal && !is_ours(strm)) {
+		static end_fn real_end;
+		if (!real_end) real_end = (end_fn)dlsym(RTLD_NEXT, "lzma_end");
+		if (real_end) real_end(strm);
+	}
+}
+
+static int routed(lzma_ret r, const char *what)
+{
+	if (r == LZMA_OK) {
+		if (verbose()) fprintf(stderr, "xz_amd preload: %s -> GPU\n", what);
+		return 1;
+	}
+	if (verbose()) fprintf(stderr, "xz_amd preload: GPU encoder declined (lzma_ret %d), using liblzma\n", (int)r);
+	return 0;
+}
+
 lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
 {
 	static enc_mt_fn real;
@@ -101,20 +129,39 @@ lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
 		real = (enc_mt_fn)dlsym(RTLD_NEXT, "lzma_stream_encoder_mt");
 	gpu_load();
 	if (gpu.h) {
-		if (strm && strm->internal && !is_ours(strm)) {
-			/* re-initialising a stream that belongs to the real library: let it free its coder */
-			static end_fn real_end;
-			if (!real_end) real_end = (end_fn)dlsym(RTLD_NEXT, "lzma_end");
-			if (real_end) real_end(strm);
-		}
-		const lzma_ret r = gpu.enc_mt(strm, options);
-		if (r == LZMA_OK) {
-			if (verbose()) fprintf(stderr, "xz_amd preload: lzma_stream_encoder_mt -> GPU\n");
-			return r;
-		}
-		if (verbose()) fprintf(stderr, "xz_amd preload: GPU encoder declined (lzma_ret %d), using liblzma\n", (int)r);
+		end_foreign(strm);
+		if (routed(gpu.enc_mt(strm, options), "lzma_stream_encoder_mt"))
+			return LZMA_OK;
 	}
 	return real ? real(strm, options) : LZMA_PROG_ERROR;
+}
+
+lzma_ret lzma_stream_encoder(lzma_stream *strm, const lzma_filter *filters, lzma_check check)
+{
+	static enc_st_fn real;
+	if (!real)
+		real = (enc_st_fn)dlsym(RTLD_NEXT, "lzma_stream_encoder");
+	gpu_load();
+	if (gpu.h && gpu.enc_st) {
+		end_foreign(strm);
+		if (routed(gpu.enc_st(strm, filters, check), "lzma_stream_encoder"))
+			return LZMA_OK;
+	}
+	return real ? real(strm, filters, check) : LZMA_PROG_ERROR;
+}
+
+lzma_ret lzma_easy_encoder(lzma_stream *strm, uint32_t preset, lzma_check check)
+{
+	static enc_easy_fn real;
+	if (!real)
+		real = (enc_easy_fn)dlsym(RTLD_NEXT, "lzma_easy_encoder");
+	gpu_load();
+	if (gpu.h && gpu.enc_easy) {
+		end_foreign(strm);
+		if (routed(gpu.enc_easy(strm, preset, check), "lzma_easy_encoder"))
+			return LZMA_OK;
+	}
+	return real ? real(strm, preset, check) : LZMA_PROG_ERROR;
 }
 
 lzma_ret lzma_code(lzma_stream *strm, lzma_action action)

@@ -49,6 +49,12 @@ void xzamd_debug_decode_counters_(uint64_t out[3])
 	for (int i = 0; i < 3; ++i) out[i] = __atomic_load_n(&dec_counters[i], __ATOMIC_RELAXED);
 }
 static void count_(int i) { __atomic_fetch_add(&dec_counters[i], 1, __ATOMIC_RELAXED); }
+/* ... and of the last decode launch of the process: [0] units, [1] Blocks, [2] the split mode of its scan */
+static uint64_t dec_last_units[3];
+void xzamd_debug_decode_units_(uint64_t out[3])
+{
+	for (int i = 0; i < 3; ++i) out[i] = __atomic_load_n(&dec_last_units[i], __ATOMIC_RELAXED);
+}
 
 static void reads_(const xzamd_dec_job *j, uint64_t n) { if (j->counts) j->counts[0] += n; }
 static void launches_(const xzamd_dec_job *j, uint64_t n) { if (j->counts) j->counts[1] += n; }
@@ -108,7 +114,11 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 	/* unit scan + decode */
 	{
 		const uint32_t nbk = (uint32_t)nb;
-		int split = d_expected != NULL && j->allow_split;
+		/* units: with the original (verification) at every state reset that carries the properties; without it at every
+		 * dictionary reset -- nothing in front of one can be referenced, so the units of a Block decode side by side with
+		 * the output itself as history.  The unit count of a Block is data: the table holds usize / 4096 + 8 per Block,
+		 * and in the plain mode a Block with more resets keeps the rest inside its last unit. */
+		int split = d_expected != NULL ? (j->allow_split ? 1 : 0) : 2;
 		uint32_t units_cap = split ? (uint32_t)(max_usize / 4096 + 8) : 1;
 		if ((uint64_t)units_cap * nb > (1ull << 27)) { split = 0; units_cap = 1; }
 		uint32_t waves = xzamd_ctx_wave_slots_(c);
@@ -124,7 +134,7 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			HIPD(xzk_malloc(&d_tiles, 4 * (nb + 1)), "hipMalloc");
 			HIPD(xzk_h2d(d_chains, hc, nb * sizeof(xzamd_dec_chain), st), "h2d chains");
 			dec_out = (uint8_t *)d_t0;
-			if (split) {
+			if (split == 1) {
 				/* The history of a span-parallel unit is what the LZMA2 encoder saw: the filtered original.  Make it with the
 				 * encoder's forward kernels when the Stream has the geometry they filter (Blocks equally long but the last,
 				 * one chain, < 2 GiB); any other Stream: unit = Block. */
@@ -179,8 +189,11 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			split = 0; units_cap = 1;
 			goto rescan;
 		}
-		const uint8_t *hist = split ? hist_src : NULL;
-		const uint32_t work = hist ? total_units : nbk;
+		const uint8_t *hist = split == 1 ? hist_src : NULL;
+		const uint32_t work = split ? total_units : nbk;
+		__atomic_store_n(&dec_last_units[0], work, __ATOMIC_RELAXED);
+		__atomic_store_n(&dec_last_units[1], nb, __ATOMIC_RELAXED);
+		__atomic_store_n(&dec_last_units[2], (uint64_t)split, __ATOMIC_RELAXED);
 		if (waves > work) waves = work ? work : 1;
 		HIPD(xzk_malloc(&d_lit, (uint64_t)waves * (0x300ull << 4) * 2), "hipMalloc");
 		HIPD(xzk_memset(d_misc, 0, 4096 + 4 * nb, st), "memset");
@@ -189,7 +202,7 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 		unsigned long long *d_mism = (unsigned long long *)((uint8_t *)d_misc + 64);
 		uint32_t *d_berr = (uint32_t *)((uint8_t *)d_misc + 4096);
 		HIPD(xzk_dec_units(d_xz, (const xzamd_dec_block *)d_blocks, nbk, (const xzamd_dec_unit *)d_units, units_cap,
-				(const uint32_t *)d_first, total_units, dec_out, hist, (uint16_t *)d_lit, waves, d_counter, d_berr, st), "decode launch");
+				(const uint32_t *)d_first, total_units, dec_out, hist, (uint16_t *)d_lit, waves, d_counter, d_berr, split == 2, st), "decode launch");
 		launches_(j, 1);
 		HIPD(xzk_d2h(h_err, d_berr, 4 * nb, st) || xzk_sync(st), "decode");
 		reads_(j, 1);

@@ -1,6 +1,7 @@
 /*
  * xzamd_frame.c -- the .xz container as the encoder writes it (doc/xz-file-format.txt): CRC32 / CRC64, VLI, Stream
- * Header, Index and Footer, Block Header, the size bounds, and stored Blocks made on the host.  Plain host code: no
+ * Header, Index and Footer, Block Header, the size bounds, stored Blocks made on the host, and the Check of a Block
+ * combined from the Checks of its segments.  Plain host code: no
  * device call and no context.
  *
  * Mirrors the container half of the reference
@@ -228,6 +229,56 @@ static uint64_t crc64_buf(const uint8_t *p, uint64_t n)
 	uint64_t c = ~0ull;
 	for (uint64_t i = 0; i < n; ++i) c = crc64_tab[(c ^ p[i]) & 0xFF] ^ (c >> 8);
 	return ~c;
+}
+
+/* ---- Check of a Block from the Checks of its segments (the single-Block Stream) ----
+ * crc(A || B) = crc(A) * x^(8 |B|) + crc(B) in GF(2)[x] modulo the polynomial: the registers of CRC32 and CRC64 start and
+ * end inverted, and the two inversions cancel in the sum exactly as in zlib's crc32_combine.  Reflected bit order: the
+ * top bit of a word is x^0.  x^(8 n) by squaring: 64 products of at most `width` shift-and-add steps, whatever n. */
+static uint64_t gf2_mul(uint64_t a, uint64_t b, uint64_t poly, uint64_t top)
+{
+	uint64_t p = 0;
+	for (uint64_t m = top; m != 0; m >>= 1) {
+		if (a & m) p ^= b;
+		b = (b & 1) ? (b >> 1) ^ poly : b >> 1;
+	}
+	return p;
+}
+
+static uint64_t crc_shift(uint64_t crc, uint64_t len, uint64_t poly, uint64_t top)
+{
+	uint64_t sq = top >> 1;                           /* x^1 */
+	for (int i = 0; i < 3; ++i) sq = gf2_mul(sq, sq, poly, top);      /* x^8: one byte */
+	uint64_t xn = top;                                /* x^0 */
+	for (; len != 0; len >>= 1) {
+		if (len & 1) xn = gf2_mul(sq, xn, poly, top);
+		sq = gf2_mul(sq, sq, poly, top);
+	}
+	return gf2_mul(xn, crc, poly, top);
+}
+
+uint32_t xzamd_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
+{
+	return (uint32_t)crc_shift(crc_a, len_b, 0xEDB88320u, 1ull << 31) ^ crc_b;
+}
+
+uint64_t xzamd_crc64_combine(uint64_t crc_a, uint64_t crc_b, uint64_t len_b)
+{
+	return crc_shift(crc_a, len_b, 0xC96C5795D7870F42ull, 1ull << 63) ^ crc_b;
+}
+
+/* Block Header of the single-Block Stream (block_header_encoder.c:73-131 with both sizes LZMA_VLI_UNKNOWN): 12 bytes,
+ * Block Flags = number of filters - 1 = 0, Filter Flags of LZMA2 */
+uint32_t xzamd_block_header_nosizes_(uint8_t out[12], uint8_t dict_byte)
+{
+	memset(out, 0, 12);
+	out[0] = 0x02;
+	out[1] = 0x00;
+	out[2] = 0x21;
+	out[3] = 0x01;
+	out[4] = dict_byte;
+	xzamd_le32_(out + 8, crc32_buf(out, 8));
+	return 12;
 }
 
 int xzamd_stored_blocks_host_(const uint8_t *in, uint64_t n, uint64_t block_size, int check,

@@ -68,6 +68,7 @@ typedef struct {
 	uint32_t span;               /* span size of the fixed plan */
 	uint32_t spb, esb, cpb;      /* per Block: span slots, encode-span slots, estimate chunks */
 	uint32_t cbytes, hs_fixed;
+	int segments;                  /* XZAMD_F_SEGMENTS: per Block only its chunk chain */
 	xzamd_mode m;
 	call_knobs k;
 	int check, whole, filtered, pipelined, defer, seeds_early;
@@ -447,8 +448,12 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		return fail(c, XZAMD_PROG_ERROR, "result of the previous deferred call not collected", 0);
 	c->err[0] = 0;
 	const uint32_t cbytes = xzamd_check_bytes_(check);
+	if (flags & XZAMD_F_SEGMENTS)
+		flags |= XZAMD_F_BLOCKS_ONLY;
 	if ((unsigned)check > 15)
 		return fail(c, XZAMD_PROG_ERROR, "check id out of range", 0);
+	if ((flags & XZAMD_F_SEGMENTS) && (check == XZAMD_CHECK_SHA256 || opt->bcj != 0))
+		return fail(c, XZAMD_OPTIONS_ERROR, "segments: the chain {LZMA2} and a Check that can be combined from parts (none, CRC32, CRC64)", 0);
 	if (cbytes == 0xFFFFFFFFu)
 		return fail(c, XZAMD_UNSUPPORTED_CHECK, "checks: none, CRC32, CRC64, SHA-256", 0);
 	{
@@ -540,6 +545,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	J->dbyte = xzamd_dict_size_byte_(opt->dict_size);
 	J->st = st; J->stb = J->pipelined ? c->st2 : st;
 	J->whole = !(flags & XZAMD_F_BLOCKS_ONLY);
+	J->segments = (flags & XZAMD_F_SEGMENTS) != 0;
 
 	memset(&c->stats, 0, sizeof(c->stats));
 	c->stats.span_size = adaptive ? 0 : J->span;
@@ -905,6 +911,43 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 	uint64_t unp;
 	uint8_t tail[48];
 	uint32_t tl = 0;
+	if (J->segments) {
+		/* XZAMD_F_SEGMENTS: only the chunk chain -- no header, end marker, padding or Check; whether the segment is stored
+		 * is decided exactly as for the Block the MT layout would make of it, so the chains are the same bytes */
+		if (J->hs_fixed + payload + pad + cbytes > J->bound) {
+			const uint64_t csz = usize + ((usize + 65535) / 65536) * 3;
+			if (opos + csz > J->out_cap) return fail(c, XZAMD_BUF_ERROR, "output buffer too small", 0);
+			uint8_t ctl = 0x01;
+			for (uint64_t ip = 0; ip < usize; ip += 65536) {
+				const uint64_t cs = usize - ip < 65536 ? usize - ip : 65536;
+				uint8_t ch[3] = { ctl, (uint8_t)((cs - 1) >> 8), (uint8_t)(cs - 1) };
+				ctl = 0x02;
+				opos = plan_lit(pl, ch, 3, opos);
+				opos = plan_seg(pl, 2, boff + ip, cs, opos);
+			}
+			++c->stats.blocks_stored;
+		} else {
+			if (opos + payload - 1 > J->out_cap) return fail(c, XZAMD_BUF_ERROR, "output buffer too small", 0);
+			for (uint32_t s = 0; s < nsp; ++s) {
+				const uint64_t slot = b * opb + s, start = otab[2 * slot];
+				if (two) {
+					const uint32_t cb = XZAMD_CHUNK_BASE((uint32_t)start, (uint32_t)slot), cc = XZAMD_CHUNK_CAP(otab[2 * slot + 1] - (uint32_t)start);
+					for (uint32_t k = 0; k < cc && hch[cb + k].usize != 0; ++k)
+						opos = plan_seg(pl, 0, XZAMD_CHUNK_OUT(hch[cb + k].in_start, cb + k), hch[cb + k].csize, opos);
+				} else
+					opos = plan_seg(pl, 0, ((start + (start >> 3) + 15) & ~15ull) + slot * XZAMD_SPAN_SLACK, sb[slot], opos);
+			}
+		}
+		const uint64_t gs = B->b0 + b;
+		if (J->binfo && gs < J->binfo_cap) {
+			J->binfo[gs].unpadded_size = check == XZAMD_CHECK_CRC64 ? bcrc[b] : check == XZAMD_CHECK_CRC32 ? (uint32_t)bcrc[b] : 0;
+			J->binfo[gs].uncompressed_size = usize;
+			J->binfo[gs].out_offset = bstart;
+			J->binfo[gs].total_size = opos - bstart;
+		}
+		*opos_io = opos;
+		return XZAMD_OK;
+	}
 	if (J->hs_fixed + payload + pad + cbytes > J->bound) {
 		/* stream_encoder_mt.c:298,316-344 -> block_buffer_encoder.c:88-162 */
 		const uint64_t csz = usize + ((usize + 65535) / 65536) * 3 + 1;

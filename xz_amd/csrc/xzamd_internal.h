@@ -22,6 +22,8 @@ int xzamd_stored_blocks_host_(const uint8_t *in, uint64_t n, uint64_t block_size
 /* test instrumentation of the device decoder: temporaries allocated for inverse filters, inverse-stage calls, forward-filter
  * launches of verification decodes (process-wide counts) */
 void xzamd_debug_decode_counters_(uint64_t out[3]);
+/* ... of the last decode launch of the process: units, Blocks, split mode of the scan (0 Block, 1 verification, 2 plain) */
+void xzamd_debug_decode_units_(uint64_t out[3]);
 
 /* The device part of a decode (xzamd_decode.c), shared by the single-Stream entry and the file entries (xzamd_file.c). */
 typedef struct {
@@ -38,7 +40,8 @@ typedef struct {
 	const uint8_t *stored;          /* XZAMD_HDR_CHECK_BYTES per Block: the stored Check */
 	const xzamd_dec_group *groups;  /* in Block order, every Block in exactly one group */
 	uint32_t ngroups;
-	int allow_split;                /* with d_expected: span-parallel units (else unit = Block; compared either way) */
+	int allow_split;                /* with d_expected: span-parallel units (else unit = Block; compared either way).  Without
+	                                 * d_expected the units always start at the dictionary resets */
 	uint64_t *mismatches;           /* optional */
 	uint64_t *counts;               /* optional: [0] += device-to-host reads, [1] += kernel-launch calls */
 } xzamd_dec_job;
@@ -57,6 +60,7 @@ XZAMD_HIDDEN uint8_t xzamd_dict_size_byte_(uint32_t dict_size);
 XZAMD_HIDDEN uint32_t xzamd_prefilter_list_(const xzamd_lzma_options *opt, uint32_t pre[XZAMD_PREFILTERS_MAX]);
 XZAMD_HIDDEN int xzamd_prefilter_valid_(uint32_t pre);
 XZAMD_HIDDEN uint32_t xzamd_block_header_size_(uint64_t csize, uint64_t usize, const xzamd_lzma_options *opt);
+XZAMD_HIDDEN uint32_t xzamd_block_header_nosizes_(uint8_t out[12], uint8_t dict_byte);
 XZAMD_HIDDEN void xzamd_block_header_put_(uint8_t *out, uint32_t hs, uint64_t csize, uint64_t usize, uint8_t dict_byte,
 		const xzamd_lzma_options *opt);
 

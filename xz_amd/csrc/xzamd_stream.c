@@ -12,6 +12,8 @@
  *   lzma_stream_encoder_mt_memusage <- stream_encoder_mt.c:1231
  *
  *   lzma_filters_update     <- stream_encoder_mt.c:914-950 (between Blocks only)
+ *   lzma_stream_encoder     <- common/stream_encoder.c:341 (init :285-338, stream_encode :79-209)
+ *   lzma_easy_encoder       <- common/easy_encoder.c
  *   lzma_mt_block_size, lzma_cputhreads <- filter_encoder.c:270, hardware_cputhreads.c
  *
  * stream_encode_mt() (:717-883) copies caller input into per-worker Block
@@ -27,6 +29,12 @@
  * encode and D2H of consecutive batches overlap).  lzma_mt.timeout bounds the
  * time a call may wait for the workers, LZMA_FULL_BARRIER returns once the
  * input is handed over (:803-807).
+ *
+ * The single-threaded entry points (lzma_stream_encoder, lzma_easy_encoder) run the same engine in `single` mode: the
+ * Stream holds one Block per full flush, its Block Header carries no sizes (the input length is unknown when it is
+ * written), and the Block's LZMA2 data is made of SEGMENTS -- what would be the Blocks of the MT layout, encoded by the
+ * same jobs with XZAMD_F_SEGMENTS: chunk chains that each start with a dictionary reset, concatenated, one end marker
+ * behind the last.  LZMA_SYNC_FLUSH ends the current segment where the input stands.
  */
 #include "../../include/xz_amd.h"
 #include "../../include/xz_amd_lzma.h"
@@ -125,6 +133,11 @@ struct lzma_internal_s {
 	uint64_t *rec; uint64_t nrec, rec_cap;
 	uint64_t progress_in, progress_out;
 	const lzma_allocator *allocator;
+	/* single mode (lzma_stream_encoder): block_size is the segment size */
+	int single;
+	int blk_open;                /* Block Header handed to the output queue, end of the Block not yet */
+	uint64_t blk_csize, blk_usize, blk_crc;       /* of the open Block: chunk chains so far, their input, its Check so far */
+	uint64_t segment_env;        /* XZAMD_SEGMENT_KIB << 10, 0 = lzma_mt_block_size of the chain */
 };
 
 static void *a_alloc(const lzma_allocator *a, size_t n)
@@ -331,7 +344,7 @@ static lzma_ret job_launch(lzma_internal *in, devslot *d, job *j, int io, int *r
 	void *cs = xzamd_ctx_stream_(d->ctx);
 	if (!injected && !(xzk_h2d(b->d_in, j->stage, n, cs) || xzk_sync(cs)) && (vlog("uploaded", j), 1))
 		*rc_out = xzamd_encode_device_(d->ctx, b->d_in, n, in->block_size, &j->opt, in->check,
-				XZAMD_F_BLOCKS_ONLY, b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
+				in->single ? XZAMD_F_SEGMENTS : XZAMD_F_BLOCKS_ONLY, b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
 				&j->nblocks, NULL, (nd && *nd == '1') ? NULL : deferred);
 	return LZMA_OK;
 }
@@ -357,7 +370,8 @@ static lzma_ret job_collect(lzma_internal *in, devslot *d, job *j, int io, int r
 		 * failures (XZAMD_PROG_ERROR) are never papered over this way. */
 		const char *sf = getenv("XZAMD_STORED_ON_DEVICE_ERROR");
 		uint64_t nblocks = 0;
-		if (sf && *sf == '1' && grow_pinned(&j->out, &j->out_cap, 0, xzamd_stream_buffer_bound(n, in->block_size)) == LZMA_OK
+		/* (single mode: the job's output is chunk chains inside an open Block, not Blocks: the Stream fails) */
+		if (!in->single && sf && *sf == '1' && grow_pinned(&j->out, &j->out_cap, 0, xzamd_stream_buffer_bound(n, in->block_size)) == LZMA_OK
 				&& xzamd_stored_blocks_host_(j->stage, n, in->block_size, in->check, j->out, j->out_cap, &out_size,
 						j->binfo, j->binfo_cap, &nblocks) == XZAMD_OK) {
 			if (getenv("XZAMD_VERBOSE"))
@@ -615,14 +629,26 @@ static lzma_ret parse_options(const lzma_mt *o, xzamd_lzma_options *opt, uint64_
 	return LZMA_OK;
 }
 
-lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
+/* jobs are whole Blocks (segments) of block_size bytes: the staging limit of one job */
+static void set_geometry(lzma_internal *in, uint64_t block_size)
 {
-	if (strm == NULL)
-		return LZMA_PROG_ERROR;
-	xzamd_lzma_options opt;
-	uint64_t block_size = 0;
-	int check = 0;
-	lzma_ret r = parse_options(options, &opt, &block_size, &check);
+	uint64_t batch = JOB_BYTES;
+	const char *env = getenv("XZAMD_BATCH_MIB");
+	if (env && atoll(env) > 0)
+		batch = (uint64_t)atoll(env) << 20;
+	uint64_t maxb = batch / block_size;
+	if (maxb == 0) maxb = 1;
+	if (maxb * block_size >= (1ull << 31)) maxb = ((1ull << 31) - 1) / block_size;
+	in->block_size = block_size;
+	in->stage_max = maxb * block_size;
+}
+
+/* The rest of an init call once the options are parsed (r = how that went): replace the coder of the stream, count the
+ * GPUs, start the workers.  single: lzma_stream_encoder's layout. */
+static lzma_ret encoder_init(lzma_stream *strm, lzma_ret r, const xzamd_lzma_options *opt_in, uint64_t block_size, int check,
+		uint32_t timeout, uint32_t threads, int single, uint64_t segment_env)
+{
+	const xzamd_lzma_options opt = *opt_in;
 	/* lzma_next_strm_init (common.h:401-410): re-initialising a stream replaces its coder, and an init that
 	 * fails ends the stream (lzma_end): a coder of ours must not survive in strm->internal -- an interposer
 	 * would hand it to the real liblzma next (preload.c), which would read it as its own lzma_internal */
@@ -647,9 +673,10 @@ lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
 	in->magic = XZAMD_MAGIC;
 	in->allocator = strm->allocator;
 	in->opt = opt;
-	in->block_size = block_size;
 	in->check = check;
-	in->timeout_ms = options->timeout;
+	in->timeout_ms = timeout;
+	in->single = single;
+	in->segment_env = segment_env;
 	in->sequence = ISEQ_RUN;
 	in->sseq = SEQ_HEADER;
 	in->fill = -1;
@@ -657,7 +684,7 @@ lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
 	/* one worker per visible GPU, the current device first; never more workers than lzma_mt.threads
 	 * (XZAMD_DEVICES=n caps it further) */
 	int ndev = ndev_all;
-	if ((uint32_t)ndev > options->threads) ndev = (int)options->threads;
+	if ((uint32_t)ndev > threads) ndev = (int)threads;
 	if (ndev > MAX_DEVS) ndev = MAX_DEVS;
 	{
 		const char *e = getenv("XZAMD_DEVICES");
@@ -692,14 +719,7 @@ lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
 	 * host; the 5 jobs of 34 that a 1 GiB job size deals: 602 MB/s; 3 jobs of 57: 653 MB/s).  While the end of the input is unknown (LZMA_RUN) full jobs are dealt in order; once the caller has shown
 	 * the end (FINISH / FULL_FLUSH / FULL_BARRIER) the rest is dealt evenly over the workers (stream_code, below), as
 	 * stream_encoder_mt.c:599-665 deals Blocks to threads. */
-	uint64_t batch = JOB_BYTES;
-	const char *env = getenv("XZAMD_BATCH_MIB");
-	if (env && atoll(env) > 0)
-		batch = (uint64_t)atoll(env) << 20;
-	uint64_t maxb = batch / block_size;
-	if (maxb == 0) maxb = 1;
-	if (maxb * block_size >= (1ull << 31)) maxb = ((1ull << 31) - 1) / block_size;
-	in->stage_max = maxb * block_size;
+	set_geometry(in, block_size);
 	{
 		const char *e = getenv("XZAMD_TEST_JOB_MIN_MIB");
 		in->test_job_min = e && atoi(e) > 0 ? (uint64_t)atoi(e) << 20 : 0;
@@ -732,6 +752,85 @@ lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
 	strm->total_in = 0;
 	strm->total_out = 0;
 	return LZMA_OK;
+}
+
+lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options)
+{
+	if (strm == NULL)
+		return LZMA_PROG_ERROR;
+	xzamd_lzma_options opt;
+	uint64_t block_size = 0;
+	int check = 0;
+	memset(&opt, 0, sizeof(opt));
+	const lzma_ret r = parse_options(options, &opt, &block_size, &check);
+	return encoder_init(strm, r, &opt, block_size, check, r == LZMA_OK ? options->timeout : 0, r == LZMA_OK ? options->threads : 1, 0, 0);
+}
+
+/* XZAMD_SEGMENT_KIB: segment size of the single-Block encoder in KiB (0 / unset: lzma_mt_block_size of the chain); at
+ * least 4 KiB, the smallest Block the MT path takes (a span is at least 4096 bytes), below 2 GiB */
+static uint64_t segment_env_bytes(void)
+{
+	const char *e = getenv("XZAMD_SEGMENT_KIB");
+	if (!e || atoll(e) <= 0)
+		return 0;
+	uint64_t kib = (uint64_t)atoll(e);
+	if (kib < 4) kib = 4;
+	if (kib >= (1u << 21)) kib = (1u << 21) - 1;
+	return kib << 10;
+}
+
+/* Option checks of the single-Block encoder, in the order of stream_encoder_init (stream_encoder.c:286-337: filters ==
+ * NULL, the Stream Flags, then the chain and the Check through block_encoder_init).  On top of what the MT front end
+ * declines: any filter in front of LZMA2 (its state would run over the whole Block, not per segment) and SHA-256 (not
+ * combinable from parts) are LZMA_OPTIONS_ERROR, so that an interposer stays on liblzma. */
+static lzma_ret parse_single(const lzma_filter *filters, uint32_t preset, lzma_check check_in, xzamd_lzma_options *opt,
+		uint64_t *segment, int *check, uint64_t segment_env)
+{
+	if ((unsigned)check_in > 15)
+		return LZMA_PROG_ERROR;
+	lzma_mt mt;
+	memset(&mt, 0, sizeof(mt));
+	mt.threads = 1;
+	mt.filters = filters;
+	mt.preset = preset;
+	mt.check = check_in;
+	const lzma_ret r = parse_options(&mt, opt, segment, check);
+	if (r != LZMA_OK)
+		return r;
+	if (opt->bcj != 0 || *check == LZMA_CHECK_SHA256)
+		return LZMA_OPTIONS_ERROR;
+	if (segment_env)
+		*segment = segment_env;
+	return LZMA_OK;
+}
+
+lzma_ret lzma_stream_encoder(lzma_stream *strm, const lzma_filter *filters, lzma_check check_in)
+{
+	if (strm == NULL)
+		return LZMA_PROG_ERROR;
+	xzamd_lzma_options opt;
+	uint64_t segment = 0;
+	int check = 0;
+	memset(&opt, 0, sizeof(opt));
+	const uint64_t senv = segment_env_bytes();
+	const lzma_ret r = filters == NULL ? LZMA_PROG_ERROR : parse_single(filters, 0, check_in, &opt, &segment, &check, senv);
+	return encoder_init(strm, r, &opt, segment, check, 0, LZMA_THREADS_MAX, 1, senv);
+}
+
+lzma_ret lzma_easy_encoder(lzma_stream *strm, uint32_t preset, lzma_check check_in)
+{
+	/* easy_encoder.c: lzma_easy_preset first (an invalid preset is LZMA_OPTIONS_ERROR), then stream_encoder_init */
+	if (strm == NULL)
+		return LZMA_PROG_ERROR;
+	xzamd_lzma_options opt;
+	uint64_t segment = 0;
+	int check = 0;
+	const uint64_t senv = segment_env_bytes();
+	lzma_ret r = xzamd_lzma_preset(&opt, preset) ? LZMA_OPTIONS_ERROR : LZMA_OK;
+	memset(&opt, 0, sizeof(opt));
+	if (r == LZMA_OK)
+		r = parse_single(NULL, preset, check_in, &opt, &segment, &check, senv);
+	return encoder_init(strm, r, &opt, segment, check, 0, LZMA_THREADS_MAX, 1, senv);
 }
 
 uint64_t lzma_stream_encoder_mt_memusage(const lzma_mt *options)
@@ -835,6 +934,21 @@ static int wait_workers(lzma_internal *in, int what, const struct timespec *dead
 	return rc;
 }
 
+/* room for n more Index records (lzma_index_append) */
+static lzma_ret rec_reserve(lzma_internal *in, uint64_t n)
+{
+	if (in->nrec + n > in->rec_cap) {
+		uint64_t nc = in->rec_cap ? in->rec_cap * 2 : 256;
+		while (nc < in->nrec + n) nc *= 2;
+		uint64_t *nr = (uint64_t *)a_alloc(in->allocator, nc * 2 * sizeof(uint64_t));
+		if (!nr) return LZMA_MEM_ERROR;
+		if (in->rec) { memcpy(nr, in->rec, in->nrec * 2 * sizeof(uint64_t)); a_free(in->allocator, in->rec); }
+		in->rec = nr;
+		in->rec_cap = nc;
+	}
+	return LZMA_OK;
+}
+
 /* stream_encode_mt(): stream_encoder_mt.c:717-883.  *timed_out is set when the call returns LZMA_OK only
  * because lzma_mt.timeout expired (common.c:332-335: that return does not count towards LZMA_BUF_ERROR). */
 static lzma_ret stream_code(lzma_internal *in, const uint8_t *inb, size_t *in_pos, size_t in_size,
@@ -895,20 +1009,26 @@ static lzma_ret stream_code(lzma_internal *in, const uint8_t *inb, size_t *in_po
 				if (dj->out_pos < dj->out_len)
 					return LZMA_OK;             /* output full */
 				/* Index records of this batch (lzma_index_append, :722) */
-				if (in->nrec + dj->nblocks > in->rec_cap) {
-					uint64_t nc = in->rec_cap ? in->rec_cap * 2 : 256;
-					while (nc < in->nrec + dj->nblocks) nc *= 2;
-					uint64_t *nr = (uint64_t *)a_alloc(in->allocator, nc * 2 * sizeof(uint64_t));
-					if (!nr) return LZMA_MEM_ERROR;
-					if (in->rec) { memcpy(nr, in->rec, in->nrec * 2 * sizeof(uint64_t)); a_free(in->allocator, in->rec); }
-					in->rec = nr;
-					in->rec_cap = nc;
+				if (in->single) {
+					/* the job's segments join the open Block: sizes, and its Check from theirs (xzamd_frame.c) */
+					for (uint64_t i = 0; i < dj->nblocks; ++i) {
+						const xzamd_block_info *sg = &dj->binfo[i];
+						in->blk_csize += sg->total_size;
+						in->blk_usize += sg->uncompressed_size;
+						if (in->check == LZMA_CHECK_CRC32)
+							in->blk_crc = xzamd_crc32_combine((uint32_t)in->blk_crc, (uint32_t)sg->unpadded_size, sg->uncompressed_size);
+						else if (in->check == LZMA_CHECK_CRC64)
+							in->blk_crc = xzamd_crc64_combine(in->blk_crc, sg->unpadded_size, sg->uncompressed_size);
+					}
+				} else {
+					const lzma_ret rr = rec_reserve(in, dj->nblocks);
+					if (rr != LZMA_OK) return rr;
+					for (uint64_t i = 0; i < dj->nblocks; ++i) {
+						in->rec[2 * (in->nrec + i)] = dj->binfo[i].unpadded_size;
+						in->rec[2 * (in->nrec + i) + 1] = dj->binfo[i].uncompressed_size;
+					}
+					in->nrec += dj->nblocks;
 				}
-				for (uint64_t i = 0; i < dj->nblocks; ++i) {
-					in->rec[2 * (in->nrec + i)] = dj->binfo[i].unpadded_size;
-					in->rec[2 * (in->nrec + i) + 1] = dj->binfo[i].uncompressed_size;
-				}
-				in->nrec += dj->nblocks;
 				pthread_mutex_lock(&in->mu);
 				dj->state = J_FREE;
 				dj->stage_len = 0;
@@ -917,6 +1037,15 @@ static lzma_ret stream_code(lzma_internal *in, const uint8_t *inb, size_t *in_po
 				pthread_mutex_unlock(&in->mu);
 			}
 			/* 2. take input (stream_encode_in: :599-664) */
+			if (in->single && !in->blk_open && *in_pos < in_size) {
+				/* SEQ_BLOCK_INIT (stream_encoder.c:105-146): input for a Block that is not open yet.  Its header -- no sizes:
+				 * the input length is unknown -- goes out in front of everything the jobs of this Block will deliver (step 0
+				 * runs before step 1, and every job of the Block before has been drained) */
+				in->tail_len = xzamd_block_header_nosizes_(in->tailbuf, xzamd_dict_size_byte_(in->opt.dict_size));
+				in->tail_pos = 0;
+				in->blk_open = 1;
+				in->blk_csize = in->blk_usize = in->blk_crc = 0;
+			}
 			while (*in_pos < in_size) {
 				if (in->fill < 0) {
 					pthread_mutex_lock(&in->mu);
@@ -964,6 +1093,10 @@ static lzma_ret stream_code(lzma_internal *in, const uint8_t *inb, size_t *in_po
 							job_max = ((nbr + nj - 1) / nj) * in->block_size;
 					}
 				}
+				/* single mode: segments are cut at multiples of the segment size from the last flush, however the input
+				 * arrives -- a job staged under LZMA_RUN beyond what a flush deals is filled to its next segment boundary */
+				if (in->single && j->stage_len > job_max && j->stage_len % in->block_size != 0)
+					job_max = (j->stage_len / in->block_size + 1) * in->block_size;
 				if (j->stage_len >= job_max) {          /* (a job filled under LZMA_RUN beyond what FINISH would deal) */
 					queue_fill_job(in);
 					continue;
@@ -1009,7 +1142,7 @@ static lzma_ret stream_code(lzma_internal *in, const uint8_t *inb, size_t *in_po
 			}
 			if (action == LZMA_RUN)
 				return LZMA_OK;             /* :796-801 */
-			if (action == LZMA_FULL_BARRIER)
+			if (action == LZMA_FULL_BARRIER && !in->single)
 				return LZMA_STREAM_END;     /* :803-807: the input is handed over, no waiting */
 			if (!all_drained(in)) {
 				/* LZMA_FULL_FLUSH / LZMA_FINISH wait for the output queue to empty (:809-823) */
@@ -1017,7 +1150,41 @@ static lzma_ret stream_code(lzma_internal *in, const uint8_t *inb, size_t *in_po
 				if (wait_workers(in, 1, deadline)) { *timed_out = 1; return LZMA_OK; }
 				break;
 			}
-			if (action == LZMA_FULL_FLUSH)
+			if (in->single) {
+				/* (the Block Header of a Block whose jobs are all drained has left tailbuf: step 0 runs first) */
+				if (in->tail_pos < in->tail_len)
+					break;
+				/* LZMA_SYNC_FLUSH: every byte up to here is out and decodable; the next segment starts at the next
+				 * input byte (stream_encoder.c:152-163) */
+				if (action == LZMA_SYNC_FLUSH)
+					return LZMA_STREAM_END;
+				if (in->blk_open) {
+					/* FULL_FLUSH / FULL_BARRIER / FINISH end the Block: end marker of the LZMA2 stream, Block Padding,
+					 * Check, Index record (stream_encoder.c:162-174; the single-threaded encoder treats a barrier as a
+					 * flush) */
+					uint8_t *t = in->tailbuf;
+					uint64_t tl = 0;
+					const uint64_t csize = in->blk_csize + 1;
+					t[tl++] = 0x00;
+					while ((csize + (tl - 1)) & 3) t[tl++] = 0;
+					if (in->check == LZMA_CHECK_CRC32) {
+						xzamd_le32_(t + tl, (uint32_t)in->blk_crc); tl += 4;
+					} else if (in->check == LZMA_CHECK_CRC64) {
+						xzamd_le32_(t + tl, (uint32_t)in->blk_crc);
+						xzamd_le32_(t + tl + 4, (uint32_t)(in->blk_crc >> 32)); tl += 8;
+					}
+					const lzma_ret rr = rec_reserve(in, 1);
+					if (rr != LZMA_OK) return rr;
+					in->rec[2 * in->nrec] = 12 + csize + xzamd_check_bytes_(in->check);
+					in->rec[2 * in->nrec + 1] = in->blk_usize;
+					++in->nrec;
+					in->tail_len = tl;
+					in->tail_pos = 0;
+					in->blk_open = 0;
+					break;                   /* step 0 hands it out */
+				}
+			}
+			if (action == LZMA_FULL_FLUSH || (in->single && action == LZMA_FULL_BARRIER))
 				return LZMA_STREAM_END;
 			/* LZMA_FINISH: Index + Stream Footer (:842-883) */
 			{
@@ -1066,6 +1233,23 @@ lzma_ret lzma_filters_update(lzma_stream *strm, const lzma_filter *filters)
 	lzma_internal *in = strm->internal;
 	if (in->sequence != ISEQ_RUN)
 		return LZMA_PROG_ERROR;
+	if (in->single) {
+		/* stream_encoder_update (stream_encoder.c:229-282): between Blocks -- at the start, or behind LZMA_FULL_FLUSH /
+		 * LZMA_FULL_BARRIER -- the whole chain may change, and with it the segment size.  Inside a Block the reference
+		 * changes LZMA2 options only right behind a LZMA_SYNC_FLUSH; this encoder declines there (LZMA_PROG_ERROR). */
+		if (in->blk_open || in->sseq > SEQ_BLOCKS || filters == NULL)
+			return LZMA_PROG_ERROR;
+		xzamd_lzma_options sopt;
+		uint64_t segment = 0;
+		int scheck = 0;
+		const lzma_ret sr = parse_single(filters, 0, (lzma_check)in->check, &sopt, &segment, &scheck, in->segment_env);
+		if (sr != LZMA_OK)
+			return sr;
+		/* (no Block open: every job is drained and none is being filled) */
+		in->opt = sopt;
+		set_geometry(in, segment);
+		return LZMA_OK;
+	}
 	if (in->fill >= 0 && in->jobs[in->fill].stage_len % in->block_size != 0)
 		return LZMA_PROG_ERROR;      /* in the middle of a Block */
 	lzma_mt mt;
@@ -1094,7 +1278,8 @@ lzma_ret lzma_code(lzma_stream *strm, lzma_action action)
 	if (strm == NULL || (strm->next_in == NULL && strm->avail_in != 0)
 			|| (strm->next_out == NULL && strm->avail_out != 0)
 			|| strm->internal == NULL || strm->internal->magic != XZAMD_MAGIC
-			|| (unsigned)action > LZMA_FULL_BARRIER || action == LZMA_SYNC_FLUSH)
+			|| (unsigned)action > LZMA_FULL_BARRIER
+			|| (action == LZMA_SYNC_FLUSH && !strm->internal->single))      /* supported_actions: stream_encoder.c:347-351 */
 		return LZMA_PROG_ERROR;
 	if (strm->reserved_ptr1 != NULL || strm->reserved_ptr2 != NULL || strm->reserved_ptr3 != NULL
 			|| strm->reserved_ptr4 != NULL || strm->reserved_int2 != 0 || strm->reserved_int3 != 0
@@ -1105,8 +1290,12 @@ lzma_ret lzma_code(lzma_stream *strm, lzma_action action)
 	switch (in->sequence) {
 	case ISEQ_RUN:
 		if (action == LZMA_FULL_FLUSH) in->sequence = ISEQ_FULL_FLUSH;
+		else if (action == LZMA_SYNC_FLUSH) in->sequence = ISEQ_SYNC_FLUSH;
 		else if (action == LZMA_FINISH) in->sequence = ISEQ_FINISH;
 		else if (action == LZMA_FULL_BARRIER) in->sequence = ISEQ_FULL_BARRIER;
+		break;
+	case ISEQ_SYNC_FLUSH:
+		if (action != LZMA_SYNC_FLUSH || in->avail_in != strm->avail_in) return LZMA_PROG_ERROR;
 		break;
 	case ISEQ_FULL_FLUSH:
 		if (action != LZMA_FULL_FLUSH || in->avail_in != strm->avail_in) return LZMA_PROG_ERROR;
@@ -1141,7 +1330,7 @@ lzma_ret lzma_code(lzma_stream *strm, lzma_action action)
 		}
 		break;
 	case LZMA_STREAM_END:
-		if (in->sequence == ISEQ_FULL_FLUSH || in->sequence == ISEQ_FULL_BARRIER)
+		if (in->sequence == ISEQ_SYNC_FLUSH || in->sequence == ISEQ_FULL_FLUSH || in->sequence == ISEQ_FULL_BARRIER)
 			in->sequence = ISEQ_RUN;
 		else
 			in->sequence = ISEQ_END;

@@ -1755,9 +1755,22 @@ void k_span_encode_t(xzamd_span_args a, uint32_t nspans, uint32_t* __restrict__ 
 //                    span start -- ONE continuous model per Block; <0>: tokens and the LZMA2 chunk table; <3>: snapshots.
 //   k_rc_chunks      one LANE per LZMA2 chunk: the range coder over the chunk's tokens.
 // ------------------------------------------------------------------------------------------
-template <uint32_t WMAX, bool PACKED>
+// The stage of a launch (xzk_parse_pieces picks it from `phase` and a.iter): what a piece starts from and where it ends are
+// compile-time facts of the instance, so each kernel carries the code of its own stage only -- the generic kernel kept the
+// walk, the pre-roll and the prior copy live (in registers) across the node loop of launches that never run them.
+//   SEED        phase 0: flat model, the whole seed piece; serves both halves of pinfo
+//   PART_PRIOR  XZAMD_ITER_PARTIAL: the seed's prior + warm-up walk + pre-roll, ends at part_tab; lane-0 half of pinfo
+//   PART_SNAP   PARTIAL | SNAP (part_iters > 1): from the snapshot, ends at part_tab; lane-0 half of pinfo
+//   FULL        XZAMD_ITER_SNAP: from the snapshot, the whole piece; lane-1 half of pinfo
+enum ParseStage : int { STAGE_SEED = 0, STAGE_PART_PRIOR = 1, STAGE_PART_SNAP = 2, STAGE_FULL = 3 };
+
+template <uint32_t WMAX, bool PACKED, ParseStage STAGE>
 __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const uint32_t span)
 {
+    constexpr bool SEED = STAGE == STAGE_SEED;
+    constexpr bool PRIOR = STAGE == STAGE_PART_PRIOR;                    // prior copy, warm-up walk, pre-roll
+    constexpr bool PARTIAL = STAGE == STAGE_PART_PRIOR || STAGE == STAGE_PART_SNAP;
+    constexpr bool FROM_SNAP = STAGE == STAGE_PART_SNAP || STAGE == STAGE_FULL;
     // LDS per wavefront: the DP nodes and the price tables -- 10,176 bytes at WMAX = 384 -> 16 wavefronts per CU.  The
     // probabilities of the piece's price model live in global memory (a.prior / a.lit, one slot per piece, L2-resident
     // while the piece runs): a parser window reads them once (bit-price table, length / distance tables on refresh), a
@@ -1772,12 +1785,12 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
 #endif
     const uint32_t lane = threadIdx.x;
     const uint32_t blk = span / a.max_spb;
-    const uint32_t k = span - blk * a.max_spb;
+    const uint32_t k = SEED ? 0u : span - blk * a.max_spb;               // (the kernel hands SEED slot 0 of a Block, the others never)
     const uint32_t block_start = blk * a.block_size;
     const uint32_t block_end = min(a.n, block_start + a.block_size);
     uint32_t span_start, span_end;
     uint32_t piece_end;
-    if (k == 0) {
+    if constexpr (SEED) {
         // the seed piece is the same whatever the plan says (k_span_cut: seed_chunks), so it can run before the plan exists
         span_start = block_start;
         span_end = block_end - block_start > XZAMD_SEED_LEN ? block_start + XZAMD_SEED_LEN : block_end;
@@ -1787,11 +1800,10 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
         span_start = uni(a.span_tab[2 * span]); span_end = uni(a.span_tab[2 * span + 1]);
         piece_end = span_end;
         // a partial iteration parses only the first part of the piece (oracle: part_len); symbols never cross its end
-        if (a.iter & XZAMD_ITER_PARTIAL) span_end = uni(a.part_tab[span]);
+        if constexpr (PARTIAL) span_end = uni(a.part_tab[span]);
     }
-    // from the snapshot: the price model, coder state and rep distances come from the carried model walk over the records of
+    // FROM_SNAP: the price model, coder state and rep distances come from the carried model walk over the records of
     // the partial iteration before (k_model_walk<3>: this piece's slot of a.prior / a.lit, a.snap_sr) -- no prior, no walk, no pre-roll
-    const bool from_snap = k != 0 && (a.iter & XZAMD_ITER_SNAP) != 0;
     const uint8_t* __restrict__ in = a.in;
 
     Env e;
@@ -1852,12 +1864,12 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
     {
         uint4* g4 = reinterpret_cast<uint4*>(z.gp);
         uint4* l4 = reinterpret_cast<uint4*>(z.lit);
-        if (k == 0) {
+        if constexpr (SEED) {
             const uint4 v = make_uint4(1024u, 1024u, 1024u, 1024u);
             for (uint32_t i = lane; i < XZAMD_PRIOR_WORDS / 4; i += 64) g4[i] = v;
             const uint4 vl = PLIT_FLAT4;
             for (uint32_t i = lane; i < lit_size / PLIT_PER_U4; i += 64) l4[i] = vl;
-        } else if (from_snap) {
+        } else if constexpr (FROM_SNAP) {
             const uint32_t* sr = a.snap_sr + (uint64_t)span * 8u;
             z.state = uni(sr[0]); z.rep0 = uni(sr[1]); z.rep1 = uni(sr[2]); z.rep2 = uni(sr[3]); z.rep3 = uni(sr[4]);
         } else {
@@ -1866,6 +1878,7 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
             const uint4* s4 = reinterpret_cast<const uint4*>(reinterpret_cast<const plit_t*>(a.lit) + (uint64_t)blk * a.max_spb * lit_size);
             for (uint32_t i = lane; i < lit_size / PLIT_PER_U4; i += 64) l4[i] = s4[i];
         }
+        (void)g4; (void)l4;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         wave_sync();
     }
@@ -1875,12 +1888,15 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
     // of it once more, from the prior, and throws the symbols away: the piece proper then starts with prices that have seen
     // the local data and with rep distances / a coder state like the ones the previous piece ends with.  `lim` is what the
     // parser may not cross: the piece start while pre-rolling, then the piece end.
+    // (PRIOR instances only: everywhere else `rec` is the constant true and `lim` the piece end)
     uint32_t lim = span_end;
     bool rec = true;
-    if (k != 0 && !from_snap && span_start - block_start > XZAMD_PREROLL) {
-        cur = span_start - XZAMD_PREROLL;
-        lim = span_start;
-        rec = false;
+    if constexpr (PRIOR) {
+        if (span_start - block_start > XZAMD_PREROLL) {
+            cur = span_start - XZAMD_PREROLL;
+            lim = span_start;
+            rec = false;
+        }
     }
     // Warm-up (oracle: parse_piece, ORC_WARM): the prior is what the Block's first 64 KiB teach; data that has drifted since
     // (float arrays, PCM, ...) needs more than the pre-roll to re-train the model, so the XZAMD_WARM bytes in front of the
@@ -1888,7 +1904,7 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
     // position's list record when it is cheap by a fixed rule, else a literal; each symbol adapts the model, nothing is
     // recorded, no prices, no DP.  64 positions per trip: lane = position (its longest entry, its byte, the byte before it,
     // the byte at rep0), the walk itself runs on readlanes.
-    if (k != 0 && !from_snap && span_start - block_start > XZAMD_PREROLL + XZAMD_SEED_LEN) {
+    if (PRIOR && span_start - block_start > XZAMD_PREROLL + XZAMD_SEED_LEN) {
         const uint32_t w1 = span_start - XZAMD_PREROLL;
         uint32_t x0 = w1 - block_start - XZAMD_SEED_LEN > XZAMD_WARM ? w1 - XZAMD_WARM : block_start + XZAMD_SEED_LEN;
         // the distances of the last four candidates the walk rejected as too expensive: one that comes up again is a distance a
@@ -1994,8 +2010,9 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
     uint32_t tl_st = lane < 12 ? lane : 0u;
     uint32_t tl_r0 = XZAMD_REP_UNKNOWN, tl_r1 = XZAMD_REP_UNKNOWN, tl_r2 = XZAMD_REP_UNKNOWN, tl_r3 = XZAMD_REP_UNKNOWN;
     if (rec) rc.ptab = w.ptab;                           // the price of the piece: its recorded symbols only
-    if (span_start == block_start) {
-        // encode_init (lzma_encoder.c:267-293): the first byte of a Block is a literal in the initial contexts
+    if constexpr (SEED) {
+        // encode_init (lzma_encoder.c:267-293): the first byte of a Block is a literal in the initial contexts (the seed
+        // piece is the only one that starts a Block)
         const uint32_t l3 = literal_bytes(in, block_start, 0, z);
         if (lane == 0) { a.sym_len[block_start] = 0; a.sym_dist[block_start] = l3; }
         encode_symbol_t<false, true, false, true>(rc, no_lds, z, 0, LITERAL, 1, l3);
@@ -2004,7 +2021,7 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
     }
     for (;;) {
         if (cur >= lim) {
-            if (rec) break;
+            if (!PRIOR || rec) break;
             rec = true;                                  // the pre-roll is over: the piece proper
             rc.ptab = w.ptab; rc.est = 0;
             lim = span_end;
@@ -2123,7 +2140,7 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
         if (lane < 2 && a.pinfo) {
             // lane 0: the half the walk over iteration 1's records reads, lane 1: the half the coder's walk reads (the seed
             // piece is parsed once and serves both)
-            const bool mine = k == 0 || (lane == 0) == ((a.iter & XZAMD_ITER_PARTIAL) != 0);
+            const bool mine = SEED || (lane == 0) == PARTIAL;
             if (mine) {
                 uint32_t* pi = a.pinfo + (uint64_t)span * XZAMD_PINFO_WORDS + lane * (XZAMD_PINFO_WORDS / 2);
                 pi[0] = s0 | (agree ? XZAMD_PI_STATE_OK : 0u);
@@ -2146,10 +2163,17 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
 #endif
 }
 
-template <uint32_t WMAX = WMAX_STD, bool PACKED = true>
+// One kernel per (list format, stage); each holds exactly one inlined copy of parse_piece_one -- and so one LDS pool.
+// XZAMD_WAVES_SEED (measurement knob): the seed launch is one wavefront per Block, a latency chain that occupancy does
+// nothing for; DESIGN.md 3.3 has what a lower value measured.
+#ifndef XZAMD_WAVES_SEED
+#define XZAMD_WAVES_SEED XZAMD_WAVES_OPT
+#endif
+template <uint32_t WMAX, bool PACKED, ParseStage STAGE>
 __global__ __launch_bounds__(64)
-__attribute__((amdgpu_waves_per_eu(XZAMD_WAVES_OPT, XZAMD_WAVES_OPT)))
-void k_parse_pieces(xzamd_span_args a, uint32_t nslots, int phase, uint32_t* __restrict__ counter)
+__attribute__((amdgpu_waves_per_eu(STAGE == STAGE_SEED ? XZAMD_WAVES_SEED : XZAMD_WAVES_OPT,
+                                   STAGE == STAGE_SEED ? XZAMD_WAVES_SEED : XZAMD_WAVES_OPT)))
+void k_parse_pieces(xzamd_span_args a, uint32_t nslots, uint32_t* __restrict__ counter)
 {
     for (;;) {
         uint32_t s = blockIdx.x;
@@ -2158,12 +2182,9 @@ void k_parse_pieces(xzamd_span_args a, uint32_t nslots, int phase, uint32_t* __r
             s = uni(s);
         }
         if (s >= nslots) break;
-        if (phase == 0) {
-            parse_piece_one<WMAX, PACKED>(a, s * a.max_spb);                 // s = Block: its seed piece
-        } else {
-            const uint32_t slot = a.order ? a.order[s] : s;
-            if (slot % a.max_spb != 0) parse_piece_one<WMAX, PACKED>(a, slot);
-        }
+        // SEED: s = Block, its seed piece is slot 0; the others: every slot but the seed's
+        const uint32_t slot = STAGE == STAGE_SEED ? s * a.max_spb : a.order ? a.order[s] : s;
+        if (STAGE == STAGE_SEED || slot % a.max_spb != 0) parse_piece_one<WMAX, PACKED, STAGE>(a, slot);
         if (counter == nullptr) break;
         __builtin_amdgcn_s_waitcnt(0);
         wave_sync();
@@ -2697,9 +2718,27 @@ int xzk_parse_pieces(const xzamd_span_args* a, uint32_t nblocks, int phase, uint
     const bool persist = phase != 0 && waves != 0 && counter != nullptr && waves < nitems;
     const uint32_t grid = persist ? waves : nitems;
     uint32_t* cnt = persist ? counter : nullptr;
-    // (specialised for the list format: a launch-time constant the compiler cannot see)
-    if (a->list_packed) hipLaunchKernelGGL((k_parse_pieces<WMAX_STD, true>), dim3(grid), dim3(64), 0, st, *a, nitems, phase, cnt);
-    else hipLaunchKernelGGL((k_parse_pieces<WMAX_STD, false>), dim3(grid), dim3(64), 0, st, *a, nitems, phase, cnt);
+    // (specialised for the list format and the stage: launch-time constants the compiler cannot see)
+    ParseStage stage;
+    if (phase == 0) stage = STAGE_SEED;
+    else if (a->iter == XZAMD_ITER_PARTIAL) stage = STAGE_PART_PRIOR;
+    else if (a->iter == (XZAMD_ITER_PARTIAL | XZAMD_ITER_SNAP)) stage = STAGE_PART_SNAP;
+    else if (a->iter == XZAMD_ITER_SNAP) stage = STAGE_FULL;
+    else return (int)hipErrorInvalidValue;               // (pieces in full from the prior: no launch of the pipeline asks for it)
+    if (stage != STAGE_SEED && stage != STAGE_FULL && !a->part_tab) return (int)hipErrorInvalidValue;
+    if ((stage == STAGE_PART_SNAP || stage == STAGE_FULL) && !a->snap_sr) return (int)hipErrorInvalidValue;
+#define XZK_PARSE_LAUNCH(P, S) \
+    hipLaunchKernelGGL((k_parse_pieces<WMAX_STD, P, S>), dim3(grid), dim3(64), 0, st, *a, nitems, cnt)
+#define XZK_PARSE_STAGE(S) \
+    case S: if (a->list_packed) XZK_PARSE_LAUNCH(true, S); else XZK_PARSE_LAUNCH(false, S); break
+    switch (stage) {
+        XZK_PARSE_STAGE(STAGE_SEED);
+        XZK_PARSE_STAGE(STAGE_PART_PRIOR);
+        XZK_PARSE_STAGE(STAGE_PART_SNAP);
+        XZK_PARSE_STAGE(STAGE_FULL);
+    }
+#undef XZK_PARSE_STAGE
+#undef XZK_PARSE_LAUNCH
     return (int)hipGetLastError();
 }
 

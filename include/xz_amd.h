@@ -196,6 +196,7 @@ typedef struct {
 	float ms_code;               /* two-phase: the coder's walk (bounds, chain, tokens) + the range coder, second stream */
 	float ms_iter1;              /* two-phase: the part of ms_parse spent in the partial iteration(s) and the carried walk over their records;
 	                                ms_parse - ms_iter1 = the full parse (k_parse_pieces, iteration 2): the dominant kernel */
+	float ms_verify;             /* XZAMD_F_VERIFY: the verification of the finished Stream (wall time, not part of ms_total) */
 } xzamd_stats;
 /* Stats of the last xzamd_stream_encode_device call of the context.  Under the lzma_* front end consecutive jobs of a
  * worker are pipelined (the back end of a job's last batch finishes underneath the next job's front end): there the stage
@@ -225,6 +226,24 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
  * (CRC32 zero-extended / CRC64; 0 for XZAMD_CHECK_NONE) for xzamd_crc32_combine / xzamd_crc64_combine.
  * Chain {LZMA2} and Checks none / CRC32 / CRC64 only (else XZAMD_OPTIONS_ERROR). */
 #define XZAMD_F_SEGMENTS 2u
+
+/* XZAMD_F_KEEP_RESUME: the two-phase encode (presets 4-9, default spans) exports one RESUME RECORD per encode span -- Block,
+ * offset inside the Block, lc / lp / pb, coder state, rep distances and the coder's model at the span start -- into a table
+ * the context keeps until its next encode or xzamd_ctx_destroy: what xzamd_stream_verify_device needs to decode every encode
+ * span as a unit of its own.  About encode spans x (32 + 2 x model size) bytes of device memory (16 KB per >= 256 KiB of
+ * input at lc + lp = 3), allocated only when asked for.  The single-phase modes (presets 0-3, explicit span sizes) write no
+ * records: their spans reset the state and carry the properties, which the verification decode cuts at anyway.  The bytes of
+ * the Stream do not depend on the flag.
+ * XZAMD_F_VERIFY (implies XZAMD_F_KEEP_RESUME): VERIFIED ENCODE.  Behind the last batch the finished Stream in d_out goes
+ * through xzamd_stream_verify_device against d_in before the call returns: chunk-grammar scan, span-parallel decode, Checks,
+ * comparison with the input.  Any defect returns XZAMD_DATA_ERROR, xzamd_last_error names the Block and the step,
+ * xzamd_get_verify_report has the details, and *out_size is still set: the caller never gets XZAMD_OK for a Stream the device
+ * decoder rejects or that differs from the input.  Nothing is rewritten; the caller decides what to do with the Stream.
+ * (Known at this version: a Block whose first piece is stored raw -- e.g. 512 KiB of random bytes in front of text -- can come
+ * out with its first LZMA chunk lacking the properties byte, which every decoder rejects; XZAMD_F_VERIFY is what reports it.)
+ * Either flag with XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS is XZAMD_OPTIONS_ERROR: there is no container to read. */
+#define XZAMD_F_KEEP_RESUME 4u
+#define XZAMD_F_VERIFY 8u
 
 typedef struct {
 	uint64_t unpadded_size;      /* Index record field 1 (block_util.c:45-76) */
@@ -258,6 +277,37 @@ int xzamd_stream_encode_device(xzamd_ctx *ctx,
 int xzamd_stream_decode_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, void *d_out, uint64_t out_cap,
 		uint64_t *out_size, const void *d_expected, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks,
 		void *stream);
+
+/* Verification of a Stream against its original, both in device memory: xzamd_stream_decode_device with d_expected into a
+ * temporary of original_size bytes, with the resume table the context keeps (XZAMD_F_KEEP_RESUME) when it fits the Stream
+ * -- as many Blocks of the same sizes as the encode it was kept from (nothing else is compared: ANOTHER Stream of that
+ * geometry verified while the table is kept meets records that are not its own and is XZAMD_DATA_ERROR, a false alarm;
+ * verify a Stream with the context that encoded it, or after an encode without the flag).  Then a decode unit starts at
+ * the Block's first chunk and at every LZMA2 chunk start whose offset a record names, from the record's model instead of a
+ * state reset: units = encode spans.  A record that no chunk start meets is XZAMD_DATA_ERROR (step "grammar"); a record whose
+ * contents are wrong makes its unit fail or decode other bytes, which the comparison with the original reports -- the table
+ * can cause a false alarm, never a false pass.  Without a fitting table (or for a filtered Stream of Blocks that differ in
+ * length or chain) the units are those of xzamd_stream_decode_device, and the report says so.  *report may be NULL. */
+#define XZAMD_VSTEP_NONE 0u
+#define XZAMD_VSTEP_GRAMMAR 1u      /* container framing, LZMA2 chunk grammar, resume records against the chunk starts */
+#define XZAMD_VSTEP_DECODE 2u       /* range coder, distances, chunk sizes */
+#define XZAMD_VSTEP_CHECK 3u        /* the stored Check of a Block */
+#define XZAMD_VSTEP_COMPARE 4u      /* decoded bytes differ from the original */
+typedef struct {
+	uint64_t units;              /* decode units (wavefronts' work items) */
+	uint64_t blocks;
+	uint64_t records_used;       /* resume records a unit started from */
+	uint64_t first_bad_block;    /* UINT64_MAX: none, or not attributable to a Block (framing, comparison) */
+	uint64_t mismatching_words;  /* 32-bit words of the decoded bytes that differ from the original */
+	uint32_t table_used;         /* 1: the units were cut at the kept table's records */
+	uint32_t first_bad_step;     /* XZAMD_VSTEP_* */
+	float ms_verify;             /* wall time of the call */
+	uint32_t reserved_;
+} xzamd_verify_report;
+int xzamd_stream_verify_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size,
+		xzamd_verify_report *report, void *stream);
+/* The report of the context's last verification (xzamd_stream_verify_device or an encode with XZAMD_F_VERIFY). */
+void xzamd_get_verify_report(const xzamd_ctx *ctx, xzamd_verify_report *out);
 
 /* ---- whole .xz files: concatenated Streams, Stream Padding, file index, range decode ----
  * An .xz file is one or more Streams, each followed by Stream Padding (zero bytes, a multiple of four): what `xz -d`

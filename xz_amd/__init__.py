@@ -19,6 +19,10 @@ SPAN_DEFAULT = 0
 SPAN_AUTO = 1
 F_BLOCKS_ONLY = 1
 F_SEGMENTS = 2
+F_KEEP_RESUME = 4
+F_VERIFY = 8
+VSTEPS = ("none", "grammar", "decode", "check", "compare")     # XZAMD_VSTEP_*
+NO_BLOCK = 0xFFFFFFFFFFFFFFFF
 BCJ_X86 = 4
 BCJ_ARM64 = 0x0A
 BCJ_RISCV = 0x0B
@@ -45,7 +49,15 @@ class Stats(C.Structure):
                 ("ms_assemble", C.c_float), ("ms_total", C.c_float), ("encode_launches", C.c_uint32),
                 ("ms_find", C.c_float), ("span_size", C.c_uint32), ("ms_find_overlapped", C.c_float),
                 ("span_cost_used", C.c_uint32), ("ms_plan", C.c_float), ("wave_slots", C.c_uint32),
-                ("enc_spans", C.c_uint64), ("ms_seed", C.c_float), ("ms_parse", C.c_float), ("ms_code", C.c_float), ("ms_iter1", C.c_float)]
+                ("enc_spans", C.c_uint64), ("ms_seed", C.c_float), ("ms_parse", C.c_float), ("ms_code", C.c_float), ("ms_iter1", C.c_float),
+                ("ms_verify", C.c_float)]
+
+
+class VerifyReport(C.Structure):
+    """xzamd_verify_report: what the last verification of a context found."""
+    _fields_ = [("units", C.c_uint64), ("blocks", C.c_uint64), ("records_used", C.c_uint64), ("first_bad_block", C.c_uint64),
+                ("mismatching_words", C.c_uint64), ("table_used", C.c_uint32), ("first_bad_step", C.c_uint32),
+                ("ms_verify", C.c_float), ("reserved_", C.c_uint32)]
 
 
 class BlockInfo(C.Structure):
@@ -127,6 +139,13 @@ def lib():
             l.xzamd_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
             l.xzamd_crc64_combine.restype = C.c_uint64
             l.xzamd_crc64_combine.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+        if hasattr(l, "xzamd_stream_verify_device"):    # (an older library lacks the verified encode)
+            l.xzamd_stream_verify_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                     C.POINTER(VerifyReport), C.c_void_p]
+            l.xzamd_get_verify_report.restype = None
+            l.xzamd_get_verify_report.argtypes = [C.c_void_p, C.POINTER(VerifyReport)]
+            l.xzamd_debug_resume_poke_.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32]
+            l.xzamd_debug_resume_peek_.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         l.xzamd_debug_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         l.xzamd_trace_enable.argtypes = [C.c_void_p, C.c_uint32]
         l.xzamd_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -267,10 +286,18 @@ class Encoder:
         return s
 
     def encode(self, data, opts=None, preset=6, block_size=0, check=CHECK_CRC64,
-               span_size=None, blocks_only=False, out=None):
+               span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0):
         """Encode a CUDA uint8 tensor into an .xz Stream (CUDA uint8 tensor).
 
         Returns (out_tensor_view, block_infos). Runs on torch's current stream.
+
+        keep_resume: the context keeps the resume table of this encode (one record per encode span) for `verify`.
+        verify: verified encode -- the finished Stream is decoded on the device, span-parallel with that table, and
+        compared with `data` before the call returns; a defect raises XzAmdError with code 9 (`.stream` = the Stream
+        as written, `verify_report()` = the details).  `flags`: further XZAMD_F_* bits.
+
+        Every XzAmdError raised here carries `code` (the XZAMD_* value; it used to be None for encode failures) and
+        `stream` (what was written: empty unless the failure is a verification defect).
         """
         import torch
         assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
@@ -296,12 +323,62 @@ class Encoder:
             cur.synchronize()
         rc = lib().xzamd_stream_encode_device(
             self._ctx, C.c_void_p(data.data_ptr()), n, bs, C.byref(opts), check,
-            F_BLOCKS_ONLY if blocks_only else 0, C.c_void_p(out.data_ptr()), out.numel(),
+            (F_BLOCKS_ONLY if blocks_only else 0) | (F_VERIFY if verify else 0) | (F_KEEP_RESUME if keep_resume else 0) | flags,
+            C.c_void_p(out.data_ptr()), out.numel(),
             C.byref(out_size), binfo, max(nblocks, 1), C.byref(nb), C.c_void_p(stream))
         if rc != 0:
-            raise XzAmdError(f"xzamd_stream_encode_device failed ({rc}): "
-                             f"{lib().xzamd_last_error(self._ctx).decode()}")
+            err = XzAmdError(f"xzamd_stream_encode_device failed ({rc}): "
+                             f"{lib().xzamd_last_error(self._ctx).decode()}", rc)
+            err.stream = out[: out_size.value]
+            raise err
         return out[: out_size.value], list(binfo)[: nb.value]
+
+    def verify_report(self):
+        """The report of this context's last verification (`verify`, or an encode with verify=True) as a dict named like
+        the fields of xzamd_verify_report; first_bad_step as one of VSTEPS, first_bad_block None when there is none."""
+        r = VerifyReport()
+        lib().xzamd_get_verify_report(self._ctx, C.byref(r))
+        d = {n: getattr(r, n) for n in ("units", "blocks", "records_used", "mismatching_words", "ms_verify")}
+        d["table_used"] = bool(r.table_used)
+        d["first_bad_block"] = None if r.first_bad_block == NO_BLOCK else r.first_bad_block
+        d["first_bad_step"] = VSTEPS[r.first_bad_step] if r.first_bad_step < len(VSTEPS) else str(r.first_bad_step)
+        return d
+
+    def verify(self, xz, original):
+        """Verify an .xz Stream against its original (CUDA uint8 tensors): device decode with the units of the resume
+        table kept by the last encode(keep_resume=True) of this context when it fits, Checks, comparison.  Returns the
+        report (`verify_report`); a defect raises XzAmdError with code 9."""
+        import torch
+        for t in (xz, original):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == xz.device
+        torch.cuda.current_stream(xz.device).synchronize()
+        rc = lib().xzamd_stream_verify_device(self._ctx, C.c_void_p(xz.data_ptr()), xz.numel(),
+                                              C.c_void_p(original.data_ptr()), original.numel(), None, None)
+        if rc != 0:
+            raise XzAmdError(f"xzamd_stream_verify_device failed ({rc})" + self._detail(), rc)
+        return self.verify_report()
+
+    def debug_resume_records(self):
+        """Test instrumentation: records of the kept resume table (0: none kept)."""
+        n = C.c_uint32(0)
+        lib().xzamd_debug_resume_peek_(self._ctx, 0, None, C.byref(n))
+        return n.value
+
+    def debug_resume_peek(self, record):
+        """Test instrumentation: header of a record of the kept table as a dict (block, upos, lc, lp, pb, kind, state, rep)."""
+        h = (C.c_uint32 * 8)()
+        rc = lib().xzamd_debug_resume_peek_(self._ctx, record, h, None)
+        if rc != 0:
+            raise XzAmdError(f"resume_peek({record}) failed: {rc}", rc)
+        return {"block": h[0], "upos": h[1], "lc": h[2] & 0xFF, "lp": (h[2] >> 8) & 0xFF, "pb": (h[2] >> 16) & 0xFF,
+                "kind": h[2] >> 24, "state": h[3], "rep": tuple(h[4:8])}
+
+    def debug_resume_poke(self, record, field, value=0):
+        """Test instrumentation: overwrite a field of a record of the kept table: "upos", "kind", "state", or "model"
+        (all 1024s)."""
+        rc = lib().xzamd_debug_resume_poke_(self._ctx, record, ("upos", "kind", "state", "model").index(field), value)
+        if rc != 0:
+            raise XzAmdError(f"resume_poke({record}, {field}) failed: {rc}", rc)
 
     def decode(self, xz, out_cap, expected=None):
         """Decode an .xz Stream held in a CUDA uint8 tensor on the device: the chains {LZMA2} and {up to three of BCJ |

@@ -91,6 +91,8 @@ typedef struct {
 	uint32_t model_slots_pad;    /* probabilities of the model, rounded up to 64 */
 	uint32_t log_cap;            /* 0 = XZAMD_LOG_CAP; tests (XZAMD_TEST_LOG_CAP): fewer logged bits per span and probability, to reach the
 	                                "not merged: the rest of the Block is not carried" fall-back on ordinary data */
+	uint32_t *resume_sr;         /* optional (resume table asked for), 8 x u32 per encode-span slot: what the token walk (k_model_syms)
+	                                actually started from: [0] coder state, [1..4] rep distances, [5] XZAMD_RK_* */
 } xzamd_span_args;
 #define XZAMD_ITER_PARTIAL 1u       /* parse only the first part (part_tab) of every piece but the seed */
 #define XZAMD_ITER_SNAP 2u          /* every piece but the seed starts from its snapshot (else: the seed's prior + walk + pre-roll) */
@@ -143,6 +145,37 @@ typedef struct xzamd_chunk {
 #define XZAMD_SPAN_SLACK 4112u      /* 4096 + 16 bytes of scratch per span slot on top of 9/8 of the input */
 #define XZAMD_EST_CHUNK 4096u       /* positions per work estimate of the span plan */
 #define XZAMD_SPAN_MAX (1u << 20)   /* longest cost-balanced span (oracle: ORC_SPAN_MAX) */
+
+/* ---- resume table (verified encode): one record per encode span, in Stream order (by Block, then by span) ----
+ * A record is what a decoder needs to start at the span's first LZMA2 chunk on its own: XZAMD_RESUME_HDR bytes of header and
+ * the model at the span start, model_slots_pad x u16.  The coder's model (P_* of lzma_kernels.hip) and the decoder's (D_* of
+ * lzma_decode.hip) index their probabilities alike -- both restate lzma_common.h / lzma_decoder.c: the offsets below, the
+ * literal coders behind them -- so the export copies the model as it is; each unit asserts the offsets.  No compressed offset:
+ * the decoder's chunk scan finds the place (k_dec_scan, split 3). */
+typedef struct {
+	uint32_t block;              /* Block of the Stream */
+	uint32_t upos;               /* the span's first byte inside its Block */
+	uint8_t lc, lp, pb;
+	uint8_t kind;                /* XZAMD_RK_* */
+	uint32_t state;              /* coder state the span starts in */
+	uint32_t rep[4];             /* rep distances, zero-based (XZAMD_REP_UNKNOWN: not named by the piece in front; never coded) */
+} xzamd_resume_hdr;
+#define XZAMD_RESUME_HDR 32u
+#define XZAMD_RESUME_KIND_OFF 11u   /* byte offset of `kind` */
+#define XZAMD_RESUME_BYTES(model_slots_pad) (XZAMD_RESUME_HDR + 2u * (model_slots_pad))
+#define XZAMD_RK_RESET 0u           /* state reset + properties at the span start: nothing carried */
+#define XZAMD_RK_CARRIED 1u         /* model, state and rep distances continue the span in front */
+#define XZAMD_RK_FLAT 2u            /* state reset without properties (behind a stored piece) */
+#define XZAMD_RK_VOID 3u            /* the Block went out in the stored form: its records match nothing and are skipped */
+#define XZAMD_RESUME_NONE 0xFFFFFFFFu
+#define XZAMD_MODEL_OFFSETS { 0u, 192u, 204u, 216u, 228u, 240u, 432u, 688u, 802u, 818u, 1332u, 1846u }  /* is_match, is_rep, is_rep0,
+                                       is_rep1, is_rep2, is_rep0_long, dist_slot, dist_special, dist_align, match_len, rep_len, literal */
+/* Records of the encode spans of a batch (a->resume_sr, a->cb_start, a->cb_carry of the coder's buffer set; after
+ * xzk_encode_syms): slot blk * max_esb + k -> record rec_base + (encode spans of the batch's Blocks in front) + k of `table`
+ * (records of XZAMD_RESUME_BYTES(a->model_slots_pad) bytes); a record index >= rec_cap is not written.  block0 = Stream index
+ * of the batch's first Block. */
+int xzk_resume_export(const xzamd_span_args *a, uint32_t nblocks, uint32_t block0, uint8_t *table, uint32_t rec_base,
+		uint32_t rec_cap, void *stream);
 
 /* One gather segment of the final assembly. kind 0: src is an offset into the span scratch,
  * 1: into the literal-bytes buffer prepared by the host, 2: into the batch input (raw). */
@@ -215,7 +248,7 @@ typedef struct {
 	uint32_t dict_size;
 	uint32_t nunits;     /* out (k_dec_scan) */
 	uint32_t error;      /* out: 0 = fine */
-	uint32_t pad_;
+	uint32_t nrecs;      /* out (k_dec_scan, split 3): resume records its units opened at */
 } xzamd_dec_block;
 
 typedef struct {
@@ -223,18 +256,24 @@ typedef struct {
 	uint64_t upos;       /* offset of its first byte inside the Block */
 	uint32_t block;
 	uint32_t dbase;      /* Block offset of the last dictionary reset at or before the unit */
+	uint32_t rec;        /* resume record the unit starts from (split 3), or XZAMD_RESUME_NONE */
+	uint32_t pad_;
 } xzamd_dec_unit;
 
 /* split: 0 = one unit per Block; 1 = a unit at every chunk that resets the state and carries the properties (verification
  * decode: history is the original; a full unit table is error 11); 2 = a unit at every chunk that resets the dictionary
- * (plain decode; once the table is full, further resets stay inside the last unit) */
+ * (plain decode; once the table is full, further resets stay inside the last unit); 3 = verification decode with a resume
+ * table (d_rec: nrec records of rec_stride bytes, sorted by Block then upos): a unit at the Block's first chunk and at every
+ * chunk start whose Block offset is the upos of the Block's next record; a record that is not met there is error 13 */
 int xzk_dec_scan(const uint8_t *d_xz, xzamd_dec_block *d_blocks, uint32_t nblocks, xzamd_dec_unit *d_units,
-		uint32_t units_cap, int split, void *stream);
+		uint32_t units_cap, int split, const uint8_t *d_rec, uint32_t rec_stride, uint32_t nrec, void *stream);
 /* d_expected: one wavefront per unit, history read from it.  Else per_unit != 0: one wavefront per unit (units that start
  * at dictionary resets, split 2), history = d_out; per_unit == 0: one wavefront per Block. */
+/* d_rec (split 3 only, else NULL): a unit with a record starts from it instead of from a state reset. */
 int xzk_dec_units(const uint8_t *d_xz, const xzamd_dec_block *d_blocks, uint32_t nblocks, const xzamd_dec_unit *d_units,
 		uint32_t units_cap, const uint32_t *d_unit_first, uint32_t total_units, uint8_t *d_out, const uint8_t *d_expected,
-		uint16_t *d_lit_pool, uint32_t waves, uint32_t *d_counter, uint32_t *d_block_err, int per_unit, void *stream);
+		uint16_t *d_lit_pool, uint32_t waves, uint32_t *d_counter, uint32_t *d_block_err, int per_unit,
+		const uint8_t *d_rec, uint32_t rec_stride, void *stream);
 int xzk_dec_compare(const uint8_t *a, const uint8_t *b, uint64_t n, unsigned long long *d_mismatches, void *stream);
 
 /* ---- inverse filters of the Block decoder (lzma_decode.hip) ----

@@ -32,12 +32,20 @@ namespace {
 enum : uint32_t {      // error codes (xzamd_dec_block.error)
     DEC_OK = 0, DEC_BAD_CONTROL = 1, DEC_NEED_DICT_RESET = 2, DEC_NEED_PROPS = 3, DEC_BAD_PROPS = 4,
     DEC_TRUNCATED = 5, DEC_SIZE_MISMATCH = 6, DEC_BAD_DISTANCE = 7, DEC_RC_INIT = 8, DEC_RC_END = 9,
-    DEC_CHUNK_OVERRUN = 10, DEC_UNIT_OVERFLOW = 11, DEC_MISMATCH = 12
+    DEC_CHUNK_OVERRUN = 10, DEC_UNIT_OVERFLOW = 11, DEC_MISMATCH = 12, DEC_RESUME_MISMATCH = 13
 };
+
+// header words of a resume record (xzamd_resume_hdr): [0] Block, [1] upos, [2] lc | lp << 8 | pb << 16 | kind << 24,
+// [3] state, [4..7] rep distances
+__device__ __forceinline__ const uint32_t* rec_hdr(const uint8_t* tab, uint32_t stride, uint32_t r)
+{
+    return reinterpret_cast<const uint32_t*>(tab + (uint64_t)r * stride);
+}
 
 // One thread per Block: walk the LZMA2 chunk chain, validate the grammar, list the units.
 __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz, xzamd_dec_block* __restrict__ blocks,
-        uint32_t nblocks, xzamd_dec_unit* __restrict__ units, uint32_t units_cap, int split)
+        uint32_t nblocks, xzamd_dec_unit* __restrict__ units, uint32_t units_cap, int split,
+        const uint8_t* __restrict__ rec_tab, uint32_t rec_stride, uint32_t nrec)
 {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nblocks) return;
@@ -48,6 +56,14 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
     uint64_t dbase = 0;                     // Block offset of the last dictionary reset
     bool need_dict_reset = true, need_props = true, ended = false;
     xzamd_dec_unit* U = units + (uint64_t)b * units_cap;
+    // split 3: the Block's slice of the sorted records starts at the first record of a Block >= b; `r` is its cursor.  A
+    // record is only ever COMPARED here (Block, upos) -- nothing of it becomes an address before a chunk start has met it.
+    uint32_t r = 0, nrecs = 0;
+    if (split == 3) {
+        uint32_t lo = 0, hi = nrec;
+        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (rec_hdr(rec_tab, rec_stride, mid)[0] < b) lo = mid + 1; else hi = mid; }
+        r = lo;
+    }
     while (c < B.csize) {
         const uint32_t ctl = p[c];
         if (ctl == 0x00) { ++c; ended = true; break; }
@@ -82,18 +98,36 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
         // split 2: the unit count is data.  A full table is no error there: further resets stay inside the last unit
         // (decode_units follows a dictionary reset in the middle of a unit)
         if (starts_unit && split == 2 && nunits == units_cap) starts_unit = false;
+        uint32_t urec = XZAMD_RESUME_NONE;
+        if (split == 3) {
+            // (the records of a Block that went out stored match nothing: skipped)
+            while (r < nrec && rec_hdr(rec_tab, rec_stride, r)[0] == b && (rec_hdr(rec_tab, rec_stride, r)[2] >> 24) == XZAMD_RK_VOID) ++r;
+            if (r < nrec && rec_hdr(rec_tab, rec_stride, r)[0] == b) {
+                const uint32_t ru = rec_hdr(rec_tab, rec_stride, r)[1];
+                if (ru == u) { starts_unit = true; urec = r; ++r; ++nrecs; }
+                else if (ru < u) { err = DEC_RESUME_MISMATCH; break; }      // no chunk starts where the record says its span does
+            }
+        }
         if (starts_unit) {
             if (nunits == units_cap) { err = DEC_UNIT_OVERFLOW; break; }
             U[nunits].cpos = B.cpos + c;
             U[nunits].upos = u;
             U[nunits].block = b;
             U[nunits].dbase = (uint32_t)dbase;
+            U[nunits].rec = urec;
+            U[nunits].pad_ = 0;
             ++nunits;
         }
         c += hs + cs;
         u += us;
     }
     if (err == DEC_OK && (!ended || c != B.csize || u != B.usize)) err = DEC_SIZE_MISMATCH;
+    if (err == DEC_OK && split == 3) {
+        // a record left over: its span start lies behind the Block's last chunk
+        while (r < nrec && rec_hdr(rec_tab, rec_stride, r)[0] == b && (rec_hdr(rec_tab, rec_stride, r)[2] >> 24) == XZAMD_RK_VOID) ++r;
+        if (r < nrec && rec_hdr(rec_tab, rec_stride, r)[0] == b) err = DEC_RESUME_MISMATCH;
+    }
+    B.nrecs = nrecs;
     B.nunits = nunits;
     B.error = err;
 }
@@ -215,12 +249,17 @@ __device__ __forceinline__ uint8_t dict_byte(const uint8_t* src, uint64_t off)
     return __hip_atomic_load(src + off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+constexpr uint32_t offs[] = XZAMD_MODEL_OFFSETS;
+
 // Decode the units [u0, u1) of one Block in order.  `hist` = where bytes before the current position are
 // read from: the output itself (plain decode) or the original data (verification decode).
 __device__ __noinline__ void decode_units(const uint8_t* __restrict__ xz, const xzamd_dec_block& B, const xzamd_dec_unit* U,
         uint32_t u0, uint32_t u1, uint8_t* __restrict__ out, const uint8_t* hist, bool plain, uint16_t* probs, uint16_t* lit,
-        uint32_t* err_out)
+        uint32_t* err_out, const uint8_t* __restrict__ rec_tab, uint32_t rec_stride)
 {
+    static_assert(offs[0] == D_IS_MATCH && offs[1] == D_IS_REP && offs[2] == D_IS_REP0 && offs[3] == D_IS_REP1 && offs[4] == D_IS_REP2
+            && offs[5] == D_IS_REP0_LONG && offs[6] == D_DIST_SLOT && offs[7] == D_DIST_SPECIAL && offs[8] == D_DIST_ALIGN
+            && offs[9] == D_MATCH_LEN && offs[10] == D_REP_LEN && offs[11] == D_TOTAL, "the layout the resume records are written in");
     const uint32_t lane = threadIdx.x;
     uint8_t* const bout = out + B.upos;                 // this Block's output
     const uint8_t* const bhist = hist + B.upos;         // this Block's history source
@@ -232,6 +271,45 @@ __device__ __noinline__ void decode_units(const uint8_t* __restrict__ xz, const 
         uint64_t dbase = U[ui].dbase;                   // bytes before it are outside the dictionary (lz_decoder.h:195-198)
         const uint64_t c_end = ui + 1 < B.nunits ? U[ui + 1].cpos - B.cpos : B.csize;
         const uint8_t* p = xz + B.cpos;
+        const uint32_t urec = rec_tab != nullptr ? uni(U[ui].rec) : XZAMD_RESUME_NONE;
+        if (urec != XZAMD_RESUME_NONE) {
+            // Unit at a resume record (k_dec_scan has met it at this chunk start): properties, coder state, rep distances
+            // and the model come from the record instead of from a state reset.  What the record says is checked like
+            // stream data: values no coder can be in end the unit, and the rep distance a literal in a match state reads its
+            // match byte at lies inside the Block's data so far -- every later use of a distance passes the test at `copy`.
+            const uint8_t* R = rec_tab + (uint64_t)urec * rec_stride;
+            const uint32_t* H = reinterpret_cast<const uint32_t*>(R);
+            const uint32_t w2 = uni(H[2]);
+            lc = w2 & 0xFFu; lp = (w2 >> 8) & 0xFFu; pb = (w2 >> 16) & 0xFFu;
+            state = uni(H[3]);
+            rep0 = uni(H[4]); rep1 = uni(H[5]); rep2 = uni(H[6]); rep3 = uni(H[7]);
+            if (lc + lp > 4 || lc > 4 || lp > 4 || pb > 4 || state >= 12) { err = DEC_RESUME_MISMATCH; break; }
+            const uint32_t nl = 0x300u << (lc + lp);
+            if ((rec_stride & 15u) != 0 || XZAMD_RESUME_HDR + 2u * (D_TOTAL + nl) > rec_stride) { err = DEC_RESUME_MISMATCH; break; }
+            if ((w2 >> 24) == XZAMD_RK_CARRIED) {
+                // 16 bytes per lane; word w holds probabilities 2 w, 2 w + 1 (D_TOTAL is even: no word straddles LDS and `lit`)
+                static_assert(D_TOTAL % 2 == 0, "model words");
+                const uint4* __restrict__ M = reinterpret_cast<const uint4*>(R + XZAMD_RESUME_HDR);
+                const uint32_t nw = (D_TOTAL + nl) / 2u;
+                uint32_t* const lit32 = reinterpret_cast<uint32_t*>(lit);
+                for (uint32_t q = lane; q * 4u < nw; q += 64) {
+                    const uint4 v = M[q];
+                    const uint32_t wv[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+                    for (uint32_t t = 0; t < 4; ++t) {
+                        const uint32_t w = q * 4u + t;
+                        if (w < D_TOTAL / 2u) { probs[2 * w] = (uint16_t)wv[t]; probs[2 * w + 1] = (uint16_t)(wv[t] >> 16); }
+                        else if (w < nw) lit32[w - D_TOTAL / 2u] = wv[t];
+                    }
+                }
+            } else {
+                for (uint32_t i = lane; i < D_TOTAL; i += 64) probs[i] = 1024;
+                for (uint32_t i = lane; i < nl; i += 64) lit[i] = 1024;
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wave_sync();
+            if (state >= 7 && (uint64_t)rep0 >= u - dbase) { err = DEC_BAD_DISTANCE; break; }
+        }
         while (c < c_end && err == DEC_OK) {
             const uint32_t ctl = uni(p[c]);
             if (ctl == 0x00) { ++c; break; }
@@ -372,7 +450,8 @@ __device__ __noinline__ void decode_units(const uint8_t* __restrict__ xz, const 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_dec_units(const uint8_t* __restrict__ xz, const xzamd_dec_block* __restrict__ blocks,
         uint32_t nblocks, const xzamd_dec_unit* __restrict__ units, uint32_t units_cap, const uint32_t* __restrict__ unit_first,
         uint32_t total_units, uint8_t* __restrict__ out, const uint8_t* __restrict__ expected,
-        uint16_t* __restrict__ lit_pool, uint32_t* __restrict__ counter, uint32_t* __restrict__ block_err, int per_unit)
+        uint16_t* __restrict__ lit_pool, uint32_t* __restrict__ counter, uint32_t* __restrict__ block_err, int per_unit,
+        const uint8_t* __restrict__ rec_tab, uint32_t rec_stride)
 {
     __shared__ uint16_t probs[D_TOTAL + 2];
     uint16_t* lit = lit_pool + (uint64_t)blockIdx.x * (0x300u << 4);
@@ -397,7 +476,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         const xzamd_dec_block& B = blocks[bi];
         if (B.error == DEC_OK)
             decode_units(xz, B, units + (uint64_t)bi * units_cap, k0, k1, out, expected ? expected : out, expected == nullptr,
-                    probs, lit, block_err + bi);
+                    probs, lit, block_err + bi, rec_tab, rec_stride);
         __builtin_amdgcn_s_waitcnt(0);
         wave_sync();
     }
@@ -880,11 +959,12 @@ __global__ __launch_bounds__(64) void k_delta_apply(xzamd_unf_args a)
 extern "C" {
 
 int xzk_dec_scan(const uint8_t* d_xz, xzamd_dec_block* d_blocks, uint32_t nblocks, xzamd_dec_unit* d_units,
-        uint32_t units_cap, int split, void* stream_)
+        uint32_t units_cap, int split, const uint8_t* d_rec, uint32_t rec_stride, uint32_t nrec, void* stream_)
 {
     if (nblocks == 0) return 0;
+    if (split == 3 && (!d_rec || rec_stride < XZAMD_RESUME_HDR || (rec_stride & 15u))) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_dec_scan, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_xz, d_blocks, nblocks,
-            d_units, units_cap, split);
+            d_units, units_cap, split, d_rec, rec_stride, split == 3 ? nrec : 0u);
     return (int)hipGetLastError();
 }
 
@@ -903,13 +983,15 @@ int xzk_dec_headers(const uint8_t* d_xz, uint64_t xz_size, const xzamd_hdr_rec* 
 
 int xzk_dec_units(const uint8_t* d_xz, const xzamd_dec_block* d_blocks, uint32_t nblocks, const xzamd_dec_unit* d_units,
         uint32_t units_cap, const uint32_t* d_unit_first, uint32_t total_units, uint8_t* d_out, const uint8_t* d_expected,
-        uint16_t* d_lit_pool, uint32_t waves, uint32_t* d_counter, uint32_t* d_block_err, int per_unit, void* stream_)
+        uint16_t* d_lit_pool, uint32_t waves, uint32_t* d_counter, uint32_t* d_block_err, int per_unit,
+        const uint8_t* d_rec, uint32_t rec_stride, void* stream_)
 {
+    if (d_rec && !d_expected) return (int)hipErrorInvalidValue;        // records belong to the verification decode
     const uint32_t total = (d_expected || per_unit) ? total_units : nblocks;
     if (total == 0) return 0;
     const uint32_t grid = waves < total ? waves : total;
     hipLaunchKernelGGL(k_dec_units, dim3(grid), dim3(64), 0, (hipStream_t)stream_, d_xz, d_blocks, nblocks, d_units, units_cap,
-            d_unit_first, total_units, d_out, d_expected, d_lit_pool, d_counter, d_block_err, per_unit);
+            d_unit_first, total_units, d_out, d_expected, d_lit_pool, d_counter, d_block_err, per_unit, d_rec, rec_stride);
     return (int)hipGetLastError();
 }
 

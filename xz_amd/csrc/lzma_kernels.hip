@@ -2308,6 +2308,12 @@ __global__ __launch_bounds__(64) void k_model_walk(xzamd_span_args a, uint32_t n
     }
     if (LITG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wave_sync();
+    if (TOKM && a.resume_sr != nullptr && lane == 0) {
+        // what this span's coder starts from, for the span's record of the resume table (k_resume_export)
+        uint32_t* sr = a.resume_sr + (uint64_t)slot * 8u;
+        sr[0] = z.state; sr[1] = z.rep0; sr[2] = z.rep1; sr[3] = z.rep2; sr[4] = z.rep3;
+        sr[5] = k == 0 ? XZAMD_RK_RESET : carry;
+    }
 
     uint16_t* const tok0 = TOKM ? a.tok + XZAMD_TOK_BASE(span_start, slot) : nullptr;
     // Token budget of the span.  The buffer holds XZAMD_TOK_PER_BYTE tokens per input byte (+ 4096); a.tok_limit (tests only,
@@ -2549,6 +2555,50 @@ __global__ __launch_bounds__(256) void k_model_chain(xzamd_span_args a, uint32_t
             }
         }
     }
+}
+
+// The resume table of a verified encode: one workgroup per encode-span slot gathers what the span's coder started from
+// (a.resume_sr: k_model_syms; a.cb_start: k_model_chain) into the span's record, and compacts the slots blk * max_esb + k
+// to consecutive records (Stream order: the batches, their Blocks and the spans of a Block all come in order).  The
+// model is copied as it is, 16 bytes per lane: coder and decoder index it alike (kernels_api.h).
+static_assert(XZAMD_RK_RESET == 0u && XZAMD_RK_CARRIED == 1u && XZAMD_RK_FLAT == 2u, "record kinds = the values of cb_carry");
+constexpr uint32_t offs[] = XZAMD_MODEL_OFFSETS;
+static_assert(offs[0] == P_IS_MATCH && offs[1] == P_IS_REP && offs[2] == P_IS_REP0 && offs[3] == P_IS_REP1 && offs[4] == P_IS_REP2
+            && offs[5] == P_IS_REP0_LONG && offs[6] == P_DIST_SLOT && offs[7] == P_DIST_SPECIAL && offs[8] == P_DIST_ALIGN
+            && offs[9] == P_MATCH_LEN && offs[10] == P_REP_LEN && offs[11] == P_LITERAL, "the coder's model layout");
+__global__ __launch_bounds__(256) void k_resume_export(xzamd_span_args a, uint32_t nblocks, uint32_t block0,
+        uint8_t* __restrict__ table, uint32_t rec_base, uint32_t rec_cap)
+{
+    __shared__ uint32_t part[4];
+    const uint32_t slot = blockIdx.x;
+    const uint32_t blk = slot / a.max_esb;
+    const uint32_t k = slot - blk * a.max_esb;
+    if (blk >= nblocks || k >= a.enc_cnt[blk]) return;          // (uniform over the workgroup)
+    // records of the batch's Blocks in front of this one
+    uint32_t s = 0;
+    for (uint32_t b = threadIdx.x; b < blk; b += 256) s += a.enc_cnt[b];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    const uint64_t r = (uint64_t)rec_base + part[0] + part[1] + part[2] + part[3] + k;
+    if (r >= rec_cap) return;
+    const uint32_t stride = XZAMD_RESUME_BYTES(a.model_slots_pad);
+    uint8_t* const rec = table + r * stride;
+    const uint32_t* sr = a.resume_sr + (uint64_t)slot * 8u;
+    const uint32_t kind = sr[5];
+    if (threadIdx.x < 8) {
+        const uint32_t t = threadIdx.x;
+        uint32_t w = sr[t < 3 ? 0u : t - 3u];                       // t = 3 .. 7: state, rep distances
+        if (t == 0) w = block0 + blk;
+        if (t == 1) w = a.enc_tab[2 * slot] - blk * a.block_size;
+        if (t == 2) w = a.lc | a.lp << 8 | a.pb << 16 | kind << 24;
+        reinterpret_cast<uint32_t*>(rec)[t] = w;
+    }
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(a.cb_start + (uint64_t)slot * a.model_slots_pad);
+    uint4* __restrict__ dst = reinterpret_cast<uint4*>(rec + XZAMD_RESUME_HDR);
+    const uint32_t nq = a.model_slots_pad / 8u;
+    const uint4 flat = make_uint4(0x04000400u, 0x04000400u, 0x04000400u, 0x04000400u);
+    for (uint32_t q = threadIdx.x; q < nq; q += 256) dst[q] = kind == XZAMD_RK_CARRIED ? src[q] : flat;
 }
 
 // Range coder of the two-phase mode: one LANE per LZMA2 chunk (rangecoder/range_encoder.h:136-263 per lane).  A chunk's
@@ -2795,6 +2845,18 @@ int xzk_encode_syms(const xzamd_span_args* a, uint32_t nblocks, void* stream_)
     if (walk_litg()) hipLaunchKernelGGL((k_model_walk<0, true>), dim3(nslots), dim3(64), lds, st, *a, nslots);
     else hipLaunchKernelGGL((k_model_walk<0, false>), dim3(nslots), dim3(64), lds, st, *a, nslots);
     hipLaunchKernelGGL(k_rc_chunks, dim3((nch + 63) / 64), dim3(64), 0, st, *a, nch);
+    return (int)hipGetLastError();
+}
+
+int xzk_resume_export(const xzamd_span_args* a, uint32_t nblocks, uint32_t block0, uint8_t* table, uint32_t rec_base,
+        uint32_t rec_cap, void* stream_)
+{
+    if (nblocks == 0) return 0;
+    if (!a->enc_tab || !a->enc_cnt || a->max_esb == 0 || !a->resume_sr || !a->cb_start || !table || a->model_slots_pad == 0
+            || (a->model_slots_pad & 63u))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_resume_export, dim3(nblocks * a->max_esb), dim3(256), 0, (hipStream_t)stream_, *a, nblocks, block0, table,
+            rec_base, rec_cap);
     return (int)hipGetLastError();
 }
 

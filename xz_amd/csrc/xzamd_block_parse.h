@@ -117,7 +117,7 @@ XZB_FN uint32_t xzb_header(const uint8_t *bh, uint32_t hs, uint64_t *h_csize, ui
 XZB_FN uint32_t xzb_block(const uint8_t *xz, const xzamd_hdr_rec *r, xzamd_dec_block *B, xzamd_dec_chain *ch, uint8_t *stored,
 		uint32_t *step)
 {
-	B->cpos = 0; B->csize = 0; B->upos = r->upos; B->usize = r->usize; B->dict_size = 0; B->nunits = 0; B->error = 0; B->pad_ = 0;
+	B->cpos = 0; B->csize = 0; B->upos = r->upos; B->usize = r->usize; B->dict_size = 0; B->nunits = 0; B->error = 0; B->nrecs = 0;
 	ch->n = 0;
 	for (uint32_t i = 0; i < XZAMD_DEC_FILTERS_MAX; ++i) ch->f[i] = 0;
 	for (uint32_t i = 0; i < XZAMD_HDR_CHECK_BYTES; ++i) stored[i] = 0;

@@ -36,8 +36,10 @@
 #include "kernels_api.h"
 #include "xzamd_block_parse.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 #define FORMAT_ERROR 7      /* LZMA_FORMAT_ERROR */
 
@@ -76,6 +78,21 @@ static uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1]
 #define FAILD(code, msg) do { rc = xzamd_ctx_fail_(c, (code), (msg)); goto done; } while (0)
 #define HIPD(call, msg) do { if (call) FAILD(XZAMD_DEVICE_ERROR, msg); } while (0)
 
+/* A defect of Block b found by step `vstep` (XZAMD_VSTEP_*): XZAMD_DATA_ERROR, the message names the Block, and the job's report
+ * (when it has one) keeps the first such defect */
+static int fail_block_(xzamd_ctx *c, const xzamd_dec_job *j, uint64_t b, uint32_t vstep, const char *msg)
+{
+	char buf[160];
+	if (j->report && j->report->first_bad_step == XZAMD_VSTEP_NONE) {
+		j->report->first_bad_step = vstep;
+		j->report->first_bad_block = b;
+	}
+	if (b == UINT64_MAX) return xzamd_ctx_fail_(c, XZAMD_DATA_ERROR, msg);
+	snprintf(buf, sizeof(buf), "Block %llu: %s", (unsigned long long)b, msg);
+	return xzamd_ctx_fail_(c, XZAMD_DATA_ERROR, buf);
+}
+#define FAILB(b, vstep, msg) do { rc = fail_block_(c, j, (b), (vstep), (msg)); goto done; } while (0)
+
 /* The device part of a decode: the Blocks of j->hb (parsed and validated: xzb_block) through unit scan, LZMA2 decode,
  * inverse filters, Checks (per group of Blocks = per Stream) and the comparison with the original. */
 int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
@@ -98,6 +115,7 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 	uint32_t max_nf = 0;
 	int any_filtered = 0, any_plain = 0;
 	uint64_t utotal = 0, max_usize = 0;
+	if (j->report) j->report->blocks = nb;
 	if (nb == 0) return XZAMD_OK;
 	if (nb >= (1ull << 31)) return xzamd_ctx_fail_(c, XZAMD_OPTIONS_ERROR, "too many Blocks for the device decoder");
 	for (uint64_t b = 0; b < nb; ++b) {
@@ -118,7 +136,8 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 		 * dictionary reset -- nothing in front of one can be referenced, so the units of a Block decode side by side with
 		 * the output itself as history.  The unit count of a Block is data: the table holds usize / 4096 + 8 per Block,
 		 * and in the plain mode a Block with more resets keeps the rest inside its last unit. */
-		int split = d_expected != NULL ? (j->allow_split ? 1 : 0) : 2;
+		const int with_table = d_expected != NULL && j->allow_split && j->d_rec != NULL && j->nrec != 0;
+		int split = d_expected != NULL ? (j->allow_split ? (with_table ? 3 : 1) : 0) : 2;
 		uint32_t units_cap = split ? (uint32_t)(max_usize / 4096 + 8) : 1;
 		if ((uint64_t)units_cap * nb > (1ull << 27)) { split = 0; units_cap = 1; }
 		uint32_t waves = xzamd_ctx_wave_slots_(c);
@@ -134,7 +153,7 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			HIPD(xzk_malloc(&d_tiles, 4 * (nb + 1)), "hipMalloc");
 			HIPD(xzk_h2d(d_chains, hc, nb * sizeof(xzamd_dec_chain), st), "h2d chains");
 			dec_out = (uint8_t *)d_t0;
-			if (split == 1) {
+			if (split == 1 || split == 3) {
 				/* The history of a span-parallel unit is what the LZMA2 encoder saw: the filtered original.  Make it with the
 				 * encoder's forward kernels when the Stream has the geometry they filter (Blocks equally long but the last,
 				 * one chain, < 2 GiB); any other Stream: unit = Block. */
@@ -169,17 +188,21 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 	rescan:
 		HIPD(xzk_malloc(&d_units, (uint64_t)units_cap * nb * sizeof(xzamd_dec_unit)), "hipMalloc");
 		HIPD(xzk_h2d(d_blocks, hb, nb * sizeof(xzamd_dec_block), st), "h2d blocks");
-		HIPD(xzk_dec_scan(d_xz, (xzamd_dec_block *)d_blocks, nbk, (xzamd_dec_unit *)d_units, units_cap, split, st), "scan launch");
+		HIPD(xzk_dec_scan(d_xz, (xzamd_dec_block *)d_blocks, nbk, (xzamd_dec_unit *)d_units, units_cap, split,
+				split == 3 ? j->d_rec : NULL, j->rec_stride, j->nrec, st), "scan launch");
 		launches_(j, 1);
 		HIPD(xzk_d2h(hb, d_blocks, nb * sizeof(xzamd_dec_block), st) || xzk_sync(st), "d2h blocks");
 		reads_(j, 1);
 		uint32_t total_units = 0;
+		uint64_t recs_used = 0;
 		int overflow = 0;
 		for (uint64_t b = 0; b < nb; ++b) {
 			if (hb[b].error == 11) overflow = 1;
-			else if (hb[b].error) FAILD(XZAMD_DATA_ERROR, "LZMA2 chunk grammar");
+			else if (hb[b].error == 13) FAILB(b, XZAMD_VSTEP_GRAMMAR, "a resume record names a span start that is no LZMA2 chunk start");
+			else if (hb[b].error) FAILB(b, XZAMD_VSTEP_GRAMMAR, "LZMA2 chunk grammar");
 			unit_first[b] = total_units;
 			total_units += hb[b].nunits;
+			recs_used += hb[b].nrecs;
 		}
 		unit_first[nb] = total_units;
 		if (overflow) {
@@ -189,8 +212,14 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			split = 0; units_cap = 1;
 			goto rescan;
 		}
-		const uint8_t *hist = split == 1 ? hist_src : NULL;
+		const uint8_t *hist = split == 1 || split == 3 ? hist_src : NULL;
 		const uint32_t work = split ? total_units : nbk;
+		if (j->report) {
+			j->report->units = work;
+			j->report->blocks = nb;
+			j->report->table_used = split == 3;
+			j->report->records_used = split == 3 ? recs_used : 0;
+		}
 		__atomic_store_n(&dec_last_units[0], work, __ATOMIC_RELAXED);
 		__atomic_store_n(&dec_last_units[1], nb, __ATOMIC_RELAXED);
 		__atomic_store_n(&dec_last_units[2], (uint64_t)split, __ATOMIC_RELAXED);
@@ -202,12 +231,13 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 		unsigned long long *d_mism = (unsigned long long *)((uint8_t *)d_misc + 64);
 		uint32_t *d_berr = (uint32_t *)((uint8_t *)d_misc + 4096);
 		HIPD(xzk_dec_units(d_xz, (const xzamd_dec_block *)d_blocks, nbk, (const xzamd_dec_unit *)d_units, units_cap,
-				(const uint32_t *)d_first, total_units, dec_out, hist, (uint16_t *)d_lit, waves, d_counter, d_berr, split == 2, st), "decode launch");
+				(const uint32_t *)d_first, total_units, dec_out, hist, (uint16_t *)d_lit, waves, d_counter, d_berr, split == 2,
+				split == 3 ? j->d_rec : NULL, j->rec_stride, st), "decode launch");
 		launches_(j, 1);
 		HIPD(xzk_d2h(h_err, d_berr, 4 * nb, st) || xzk_sync(st), "decode");
 		reads_(j, 1);
 		for (uint64_t b = 0; b < nb; ++b)
-			if (h_err[b]) FAILD(XZAMD_DATA_ERROR, "LZMA2 data (range coder / distances / chunk sizes)");
+			if (h_err[b]) FAILB(b, XZAMD_VSTEP_DECODE, "LZMA2 data (range coder / distances / chunk sizes)");
 		if (any_filtered) {
 			/* inverse stages, the filter next to LZMA2 first; an unfiltered Block of a mixed Stream is copied in stage 0 */
 			xzamd_unf_args ua;
@@ -317,9 +347,9 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 				if (check == XZAMD_CHECK_CRC32 || check == XZAMD_CHECK_CRC64) {
 					uint64_t sv = 0;
 					for (uint32_t i = 0; i < (check == XZAMD_CHECK_CRC32 ? 4u : 8u); ++i) sv |= (uint64_t)sb[i] << (8 * i);
-					if (h_crc[b] != sv) FAILD(XZAMD_DATA_ERROR, "Block Check mismatch");
+					if (h_crc[b] != sv) FAILB(b, XZAMD_VSTEP_CHECK, "Block Check mismatch");
 				} else if (check == XZAMD_CHECK_SHA256) {
-					if (memcmp(h_sha + 32 * b, sb, 32) != 0) FAILD(XZAMD_DATA_ERROR, "Block Check mismatch (SHA-256)");
+					if (memcmp(h_sha + 32 * b, sb, 32) != 0) FAILB(b, XZAMD_VSTEP_CHECK, "Block Check mismatch (SHA-256)");
 				}
 			}
 		}
@@ -330,7 +360,8 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			HIPD(xzk_d2h(&mm, d_mism, 8, st) || xzk_sync(st), "d2h compare");
 			reads_(j, 1);
 			if (mismatches) *mismatches = mm;
-			if (mm) FAILD(XZAMD_DATA_ERROR, "decoded bytes differ from the original");
+			if (j->report) j->report->mismatching_words = mm;
+			if (mm) FAILB(UINT64_MAX, XZAMD_VSTEP_COMPARE, "decoded bytes differ from the original");
 		}
 	}
 done:
@@ -355,9 +386,10 @@ done:
 	return rc;
 }
 
-int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size, void *d_out_, uint64_t out_cap,
+/* xzamd_stream_decode_device; `tab` / `report` (both optional): the verification of xzamd_stream_verify_device */
+static int stream_decode_(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size, void *d_out_, uint64_t out_cap,
 		uint64_t *out_size, const void *d_expected_, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks_out,
-		void *stream)
+		void *stream, const xzamd_resume_view *tab, xzamd_verify_report *report)
 {
 	if (!c || !d_xz_ || !out_size || (!d_out_ && out_cap))
 		return XZAMD_PROG_ERROR;
@@ -480,11 +512,119 @@ int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size
 		job.groups = &group; job.ngroups = 1;
 		job.allow_split = 1;
 		job.mismatches = mismatches;
+		job.report = report;
+		if (tab && tab->d_rec && tab->nrec && d_expected) {
+			/* the kept table fits when the Stream has the Blocks of the encode it was kept from: as many, of the same sizes
+			 * (the properties are the records' own; a chunk that carries others overrides them as in any decode) */
+			int fits = nb == tab->nblocks && utotal == tab->in_size;
+			for (uint64_t b = 0; fits && b < nb; ++b) {
+				const uint64_t left = tab->in_size - b * tab->block_size;
+				fits = hb[b].usize == (left < tab->block_size ? left : tab->block_size);
+			}
+			if (fits) { job.d_rec = tab->d_rec; job.rec_stride = tab->stride; job.nrec = tab->nrec; }
+		}
 		rc = xzamd_dec_run_(c, st, &job);
 	}
 done:
 	xzk_sync(st);
+	/* a defect of the container (nothing was decoded); a device or memory failure is no finding about the Stream */
+	if ((rc == XZAMD_DATA_ERROR || rc == FORMAT_ERROR) && report && report->first_bad_step == XZAMD_VSTEP_NONE)
+		report->first_bad_step = XZAMD_VSTEP_GRAMMAR;
 	free(hc); free(stored32); free(index); free(hb);
 	return rc;
+}
+
+int xzamd_stream_decode_device(xzamd_ctx *c, const void *d_xz_, uint64_t xz_size, void *d_out_, uint64_t out_cap,
+		uint64_t *out_size, const void *d_expected_, uint64_t expected_size, uint64_t *mismatches, uint64_t *nblocks_out,
+		void *stream)
+{
+	return stream_decode_(c, d_xz_, xz_size, d_out_, out_cap, out_size, d_expected_, expected_size, mismatches, nblocks_out,
+			stream, NULL, NULL);
+}
+
+int xzamd_stream_verify_device(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size,
+		xzamd_verify_report *report, void *stream)
+{
+	if (!c || !d_xz || (!d_original && original_size))
+		return XZAMD_PROG_ERROR;
+	xzamd_verify_report *rp = xzamd_ctx_report_(c);
+	xzamd_resume_view tab;
+	struct timespec t0, t1;
+	void *d_tmp = NULL;
+	uint64_t osz = 0, mm = 0, nbk = 0;
+	int rc;
+	clock_gettime(CLOCK_MONOTONIC, &t0);
+	memset(rp, 0, sizeof(*rp));
+	rp->first_bad_block = UINT64_MAX;
+	xzamd_ctx_resume_(c, &tab);
+	if (report) *report = *rp;
+	if (xzk_set_device(xzamd_ctx_device(c)))
+		return xzamd_ctx_fail_(c, XZAMD_DEVICE_ERROR, "hipSetDevice");
+	if (xzk_malloc(&d_tmp, original_size + 16))
+		return xzamd_ctx_fail_(c, XZAMD_MEM_ERROR, "hipMalloc (verification output)");
+	/* (an original of no bytes still needs a pointer for "this is a verification") */
+	rc = stream_decode_(c, d_xz, xz_size, d_tmp, original_size, &osz, d_original ? d_original : d_tmp, original_size, &mm, &nbk,
+			stream, &tab, rp);
+	if (rc == XZAMD_BUF_ERROR) {
+		rp->first_bad_step = XZAMD_VSTEP_COMPARE;
+		rc = xzamd_ctx_fail_(c, XZAMD_DATA_ERROR, "the Stream's uncompressed size differs from the size of the original");
+	}
+	xzk_free(d_tmp);
+	clock_gettime(CLOCK_MONOTONIC, &t1);
+	rp->ms_verify = (float)((double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6);
+	if (report) *report = *rp;
+	return rc;
+}
+
+int xzamd_verify_kept_(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size, void *stream)
+{
+	return xzamd_stream_verify_device(c, d_xz, xz_size, d_original, original_size, NULL, stream);
+}
+
+void xzamd_get_verify_report(const xzamd_ctx *c, xzamd_verify_report *out)
+{
+	if (!c || !out) return;
+	*out = *xzamd_ctx_report_((xzamd_ctx *)c);
+}
+
+int xzamd_debug_resume_peek_(xzamd_ctx *c, uint32_t record, uint32_t hdr_out[8], uint32_t *nrec_out)
+{
+	xzamd_resume_view tab;
+	if (!c) return XZAMD_PROG_ERROR;
+	xzamd_ctx_resume_(c, &tab);
+	if (nrec_out) *nrec_out = tab.d_rec ? tab.nrec : 0;
+	if (!hdr_out) return XZAMD_OK;
+	if (!tab.d_rec || record >= tab.nrec) return XZAMD_PROG_ERROR;
+	void *st = xzamd_ctx_stream_(c);
+	if (xzk_set_device(xzamd_ctx_device(c))) return XZAMD_DEVICE_ERROR;
+	if (xzk_d2h(hdr_out, tab.d_rec + (uint64_t)record * tab.stride, XZAMD_RESUME_HDR, st) || xzk_sync(st)) return XZAMD_DEVICE_ERROR;
+	return XZAMD_OK;
+}
+
+int xzamd_debug_resume_poke_(xzamd_ctx *c, uint32_t record, int field, uint32_t value)
+{
+	xzamd_resume_view tab;
+	if (!c) return XZAMD_PROG_ERROR;
+	xzamd_ctx_resume_(c, &tab);
+	if (!tab.d_rec || record >= tab.nrec || field < 0 || field > 3)
+		return XZAMD_PROG_ERROR;
+	void *st = xzamd_ctx_stream_(c);
+	uint8_t *rec = tab.d_rec + (uint64_t)record * tab.stride;
+	int e;
+	if (xzk_set_device(xzamd_ctx_device(c))) return XZAMD_DEVICE_ERROR;
+	if (field == 0) e = xzk_h2d(rec + 4, &value, 4, st);
+	else if (field == 1) { const uint8_t k = (uint8_t)value; e = xzk_h2d(rec + XZAMD_RESUME_KIND_OFF, &k, 1, st); }
+	else if (field == 2) e = xzk_h2d(rec + 12, &value, 4, st);
+	else {
+		const uint32_t n = (tab.stride - XZAMD_RESUME_HDR) / 2;
+		uint16_t *flat = (uint16_t *)malloc(2ull * n);
+		if (!flat) return XZAMD_MEM_ERROR;
+		for (uint32_t i = 0; i < n; ++i) flat[i] = 1024;
+		e = xzk_h2d(rec + XZAMD_RESUME_HDR, flat, 2ull * n, st);
+		if (!e) e = xzk_sync(st);
+		free(flat);
+	}
+	if (!e) e = xzk_sync(st);
+	return e ? XZAMD_DEVICE_ERROR : XZAMD_OK;
 }
 

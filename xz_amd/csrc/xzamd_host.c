@@ -72,6 +72,8 @@ typedef struct {
 	xzamd_mode m;
 	call_knobs k;
 	int check, whole, filtered, pipelined, defer, seeds_early;
+	int resume, verify;          /* XZAMD_F_KEEP_RESUME / _VERIFY on a two-phase encode: resume records are exported; verify the Stream */
+	uint32_t rec_done;           /* resume records of the batches that are through their back end */
 	uint8_t dbyte;
 	void *st, *stb;              /* front-end stream (the caller's), back-end stream (the second one when pipelined) */
 	uint64_t *rec_unp, *rec_unc;
@@ -102,6 +104,12 @@ struct xzamd_ctx {
 	dbuf cb_bnd[2], cb_log[2], cb_hdr[2], cb_start[2], cb_carry[2]; /* carried model walk: [0] over iteration 1's records (front end), [1] the coder's (back end) */
 	dbuf sym_len[2], sym_dist[2], prior, enc_tab[2], enc_cnt[2];   /* two-phase mode ([2]: one set per pipeline parity) */
 	dbuf tok, chunks, h_chunks;                                    /* coder of the two-phase mode: tokens, chunk table */
+	dbuf resume_sr;                                                /* what the token walk of every encode span started from (resume table asked for) */
+	/* The resume table of the last encode with XZAMD_F_KEEP_RESUME / _VERIFY (kernels_api.h), kept until the next encode;
+	 * not a per-batch buffer: it lives for the call and beyond */
+	dbuf resume_tab;
+	struct { int valid; uint32_t stride, nrec; uint64_t nblocks, block_size, in_size; } resume;
+	xzamd_verify_report report;                                    /* of the last verification */
 	/* pinned host buffers */
 	dbuf h_span_bytes, h_block_crc, h_segs, h_lits, h_span_tab, h_span_cnt[2], h_enc_tab[2], h_enc_cnt[2], h_err[2];
 	void *evp[2][EV_COUNT];
@@ -224,7 +232,7 @@ static void ctx_device_bufs(xzamd_ctx *c, dbuf **d, size_t *nd)
 		&c->span_bytes, &c->strip_crc, &c->block_crc, &c->segs, &c->lits, &c->trace, &c->errw, &c->errw2,
 		&c->totals, &c->span_tab[0], &c->span_tab[1], &c->span_cnt[0], &c->span_cnt[1], &c->prior, &c->enc_tab[0], &c->enc_tab[1], &c->enc_cnt[0], &c->enc_cnt[1],
 		&c->pinfo[0], &c->pinfo[1], &c->snap_sr, &c->part_tab, &c->cb_bnd[0], &c->cb_bnd[1], &c->cb_hdr[0], &c->cb_hdr[1], &c->cb_start[0], &c->cb_start[1],
-		&c->cb_carry[0], &c->cb_carry[1] };
+		&c->cb_carry[0], &c->cb_carry[1], &c->resume_sr };
 	_Static_assert(sizeof(all) / sizeof(all[0]) <= CTX_NBUF_MAX, "ctx_device_bufs: raise CTX_NBUF_MAX");
 	*nd = sizeof(all) / sizeof(all[0]);
 	memcpy(d, all, sizeof(all));
@@ -246,6 +254,7 @@ void xzamd_ctx_destroy(xzamd_ctx *c)
 	ctx_device_bufs(c, d, &nd);
 	for (size_t i = 0; i < nd; ++i)
 		if (d[i]->p) xzk_free(d[i]->p);
+	if (c->resume_tab.p) xzk_free(c->resume_tab.p);
 	dbuf *h[] = { &c->h_span_bytes, &c->h_block_crc, &c->h_segs, &c->h_lits, &c->h_span_tab, &c->h_span_cnt[0], &c->h_span_cnt[1],
 		&c->h_enc_tab[0], &c->h_enc_tab[1], &c->h_enc_cnt[0], &c->h_enc_cnt[1], &c->h_err[0], &c->h_err[1], &c->h_chunks };
 	for (size_t i = 0; i < sizeof(h) / sizeof(h[0]); ++i)
@@ -325,6 +334,21 @@ void *xzamd_ctx_stream_(xzamd_ctx *c) { return c->own_stream; }
 uint32_t xzamd_ctx_wave_slots_(const xzamd_ctx *c) { return c->wave_slots; }
 int xzamd_ctx_fail_(xzamd_ctx *c, int code, const char *what) { return fail(c, code, what, 0); }
 int xzamd_ctx_device(const xzamd_ctx *c) { return c ? c->device : -1; }
+xzamd_verify_report *xzamd_ctx_report_(xzamd_ctx *c) { return &c->report; }
+void xzamd_ctx_resume_(xzamd_ctx *c, xzamd_resume_view *v)
+{
+	memset(v, 0, sizeof(*v));
+	if (!c->resume.valid || !c->resume_tab.p) return;
+	v->d_rec = (uint8_t *)c->resume_tab.p;
+	v->stride = c->resume.stride; v->nrec = c->resume.nrec;
+	v->nblocks = c->resume.nblocks; v->block_size = c->resume.block_size; v->in_size = c->resume.in_size;
+}
+/* The resume export (lzma_kernels.hip) and the verification (xzamd_decode.c) are referred to weakly: a build of this unit
+ * on top of a kernel layer without them, or without the decoder, answers the two flags with XZAMD_OPTIONS_ERROR. */
+extern int xzk_resume_export(const xzamd_span_args *a, uint32_t nblocks, uint32_t block0, uint8_t *table, uint32_t rec_base,
+		uint32_t rec_cap, void *stream) __attribute__((weak));
+extern int xzamd_verify_kept_(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size,
+		void *stream) __attribute__((weak));
 void xzamd_get_stats(const xzamd_ctx *c, xzamd_stats *out) { *out = c->stats; }
 const char *xzamd_version(void) { return "xz_amd 0.1 (gfx950)"; }
 
@@ -452,6 +476,10 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		flags |= XZAMD_F_BLOCKS_ONLY;
 	if ((unsigned)check > 15)
 		return fail(c, XZAMD_PROG_ERROR, "check id out of range", 0);
+	if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && (flags & XZAMD_F_BLOCKS_ONLY))
+		return fail(c, XZAMD_OPTIONS_ERROR, "keep_resume / verify need a whole Stream: not with XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS", 0);
+	if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && (!xzk_resume_export || !xzamd_verify_kept_))
+		return fail(c, XZAMD_OPTIONS_ERROR, "keep_resume / verify: this build has no resume export or no device decoder", 0);
 	if ((flags & XZAMD_F_SEGMENTS) && (check == XZAMD_CHECK_SHA256 || opt->bcj != 0))
 		return fail(c, XZAMD_OPTIONS_ERROR, "segments: the chain {LZMA2} and a Check that can be combined from parts (none, CRC32, CRC64)", 0);
 	if (cbytes == 0xFFFFFFFFu)
@@ -497,7 +525,10 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	 * an allocation that fails there surfaces as an error of some later call, not as a clean out-of-memory here.  So
 	 * the batch is capped at 80 % of what is free now plus what this context already holds. */
 	{
-		const double per_byte = xzamd_work_bytes_per_byte_(opt);
+		double per_byte = xzamd_work_bytes_per_byte_(opt);
+		/* the resume table (only when asked for): one record per encode-span slot, for the whole call */
+		if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && J->m.two)
+			per_byte += (double)(XZAMD_RESUME_BYTES(J->m.model_slots) + 32u) * (double)(block_size / XZAMD_ENC_MIN_LEN + 1) / (double)block_size;
 		uint64_t free_b = 0, total_b = 0, held = 0;
 		if (xzk_mem_info(&free_b, &total_b) == 0 && total_b != 0) {
 			dbuf *d[CTX_NBUF_MAX];
@@ -546,6 +577,21 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	J->st = st; J->stb = J->pipelined ? c->st2 : st;
 	J->whole = !(flags & XZAMD_F_BLOCKS_ONLY);
 	J->segments = (flags & XZAMD_F_SEGMENTS) != 0;
+	J->resume = (flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && two;
+	J->verify = (flags & XZAMD_F_VERIFY) != 0;
+	/* the table of the encode before is that encode's: gone with this one (its memory too, unless this call fills it again) */
+	c->resume.valid = 0;
+	if (c->resume_tab.p && !J->resume && !c->pend.active) {
+		xzk_free(c->resume_tab.p);
+		c->resume_tab.p = NULL; c->resume_tab.cap = 0;
+	}
+	if (J->resume) {
+		const uint64_t cap = total_blocks * J->esb;
+		if (cap >= 0xFFFFFFFFull)
+			return fail(c, XZAMD_OPTIONS_ERROR, "too many encode spans for a resume table", 0);
+		int r = dgrow(c, &c->resume_tab, (cap ? cap : 1) * XZAMD_RESUME_BYTES(J->m.model_slots), 0);
+		if (r) return r;
+	}
 
 	memset(&c->stats, 0, sizeof(c->stats));
 	c->stats.span_size = adaptive ? 0 : J->span;
@@ -679,6 +725,7 @@ static int batch_reserve(xzamd_ctx *c, const job_env *J, const batch_run *B)
 			NEED(cb_start[f], 2 * mslots * nenc + 16, 0);
 			NEED(cb_carry[f], 4 * nenc + 16, 0);
 		}
+		if (J->resume) NEED(resume_sr, 32 * nenc + 32, 0);
 		NEED(chunks, nch * sizeof(xzamd_chunk), 0);
 		NEED(h_chunks, nch * sizeof(xzamd_chunk), 1);
 	}
@@ -761,6 +808,7 @@ static void span_args_init(const xzamd_ctx *c, const job_env *J, const batch_run
 		a->snap_sr = (uint32_t *)c->snap_sr.p;
 		a->part_tab = (uint32_t *)c->part_tab.p;
 		a->model_slots_pad = J->m.model_slots;
+		a->resume_sr = J->resume ? (uint32_t *)c->resume_sr.p : NULL;
 		/* (the front end's set of the carried-walk buffers; the back end switches to its own) */
 		a->cb_bnd = (uint32_t *)c->cb_bnd[0].p; a->cb_log = (uint32_t *)c->cb_log[0].p; a->cb_hdr = (uint32_t *)c->cb_hdr[0].p;
 		a->cb_start = (uint16_t *)c->cb_start[0].p; a->cb_carry = (uint32_t *)c->cb_carry[0].p;
@@ -803,6 +851,11 @@ static int back_enqueue(xzamd_ctx *c, const job_env *J, back_args *BA)
 		a2.cb_bnd = (uint32_t *)c->cb_bnd[1].p; a2.cb_log = (uint32_t *)c->cb_log[1].p; a2.cb_hdr = (uint32_t *)c->cb_hdr[1].p;
 		a2.cb_start = (uint16_t *)c->cb_start[1].p; a2.cb_carry = (uint32_t *)c->cb_carry[1].p;
 		e = xzk_encode_syms(&a2, (uint32_t)nb, stb);
+		/* the batch's resume records, while the coder's buffer set still holds this batch (the batches' back ends run in
+		 * order: rec_done counts the records of every batch in front of this one) */
+		if (!e && J->resume)
+			e = xzk_resume_export(&a2, (uint32_t)nb, (uint32_t)B->b0, (uint8_t *)c->resume_tab.p, J->rec_done,
+					(uint32_t)(J->total_blocks * J->esb), stb);
 	}
 	xzk_event_record(ev[EV_CODE], stb);
 	if (e) return fail(c, XZAMD_DEVICE_ERROR, "encode_syms launch", e);
@@ -866,8 +919,9 @@ static int back_report(xzamd_ctx *c, const job_env *J, const batch_run *B)
 
 /* Block b of the batch at *opos of the Stream: Block Header, the coded spans in order (or the stored form), padding and
  * Check go into the gather plan; its sizes into the Index records and the caller's table. */
-static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, uint64_t b, uint64_t *opos_io)
+static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, uint64_t b, uint64_t *opos_io, int *stored_out)
 {
+	*stored_out = 0;
 	const uint64_t block_size = J->block_size;
 	const uint32_t opb = B->opb, cbytes = J->cbytes;
 	const int two = J->m.two, check = J->check, par = B->par;
@@ -926,6 +980,7 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 				opos = plan_seg(pl, 2, boff + ip, cs, opos);
 			}
 			++c->stats.blocks_stored;
+			*stored_out = 1;
 		} else {
 			if (opos + payload - 1 > J->out_cap) return fail(c, XZAMD_BUF_ERROR, "output buffer too small", 0);
 			for (uint32_t s = 0; s < nsp; ++s) {
@@ -967,6 +1022,7 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 		while ((csz + (tl - 1)) & 3) tail[tl++] = 0;
 		unp = hs + csz + cbytes;
 		++c->stats.blocks_stored;
+		*stored_out = 1;
 	} else {
 		if (opos + J->hs_fixed + payload + pad + cbytes > J->out_cap) return fail(c, XZAMD_BUF_ERROR, "output buffer too small", 0);
 		xzamd_block_header_put_(small, J->hs_fixed, payload, usize, J->dbyte, J->opt);
@@ -1056,8 +1112,19 @@ static int back_finish(xzamd_ctx *c, job_env *J, batch_run *B)
 	pl.segs = (xzamd_copy_seg *)c->h_segs.p; pl.nsegs = 0; pl.segs_cap = B->max_segs;
 	uint64_t opos = J->opos;
 	for (uint64_t b = 0; b < B->nb; ++b) {
-		rc = layout_block(c, J, B, &pl, b, &opos);
+		int stored = 0;
+		rc = layout_block(c, J, B, &pl, b, &opos, &stored);
 		if (rc != XZAMD_OK) return rc;
+		if (J->resume) {
+			/* the Block's records; one that went out stored has none of its span starts: its records are void */
+			const uint32_t cnt = ((const uint32_t *)c->h_enc_cnt[B->par].p)[b];
+			if (stored)
+				for (uint32_t k = 0; k < cnt; ++k)
+					if (xzk_memset((uint8_t *)c->resume_tab.p + (uint64_t)(J->rec_done + k) * XZAMD_RESUME_BYTES(J->m.model_slots)
+							+ XZAMD_RESUME_KIND_OFF, (int)XZAMD_RK_VOID, 1, J->stb))
+						return fail(c, XZAMD_DEVICE_ERROR, "memset resume record", 1);
+			J->rec_done += cnt;
+		}
 	}
 	J->opos = opos;
 	if (pl.nsegs > pl.segs_cap || pl.lits_len > pl.lits_cap) return fail(c, XZAMD_PROG_ERROR, "plan overflow", 0);
@@ -1464,5 +1531,15 @@ int xzamd_encode_device_(xzamd_ctx *c,
 	c->stats.in_bytes = in_size;
 	c->stats.out_bytes = J.opos;
 	*out_size = (deferred && *deferred) ? 0 : J.opos;
+	if (rc == XZAMD_OK && J.resume) {
+		c->resume.valid = 1;
+		c->resume.stride = XZAMD_RESUME_BYTES(J.m.model_slots); c->resume.nrec = J.rec_done;
+		c->resume.nblocks = J.total_blocks; c->resume.block_size = J.block_size; c->resume.in_size = in_size;
+	}
+	if (rc == XZAMD_OK && J.verify) {
+		/* verified encode: the finished Stream against the input, before the caller sees XZAMD_OK (its message and report stay) */
+		rc = xzamd_verify_kept_(c, J.d_out, J.opos, J.d_in, in_size, J.st);
+		c->stats.ms_verify = c->report.ms_verify;
+	}
 	return rc;
 }

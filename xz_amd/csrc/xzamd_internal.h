@@ -44,7 +44,29 @@ typedef struct {
 	                                 * d_expected the units always start at the dictionary resets */
 	uint64_t *mismatches;           /* optional */
 	uint64_t *counts;               /* optional: [0] += device-to-host reads, [1] += kernel-launch calls */
+	/* verification decode with a resume table (xzamd_stream_verify_device): units at the records instead of at the state resets
+	 * that carry properties -- under the geometry rule of allow_split; else the table is ignored */
+	const uint8_t *d_rec;           /* optional: nrec records of rec_stride bytes (kernels_api.h) */
+	uint32_t rec_stride, nrec;
+	xzamd_verify_report *report;    /* optional: units, Blocks, records, the first defect */
 } xzamd_dec_job;
+
+/* The resume table a context keeps of its last encode with XZAMD_F_KEEP_RESUME / XZAMD_F_VERIFY (xzamd_host.c) */
+typedef struct {
+	uint8_t *d_rec;                 /* NULL: none kept */
+	uint32_t stride, nrec;
+	uint64_t nblocks, block_size, in_size;   /* the Stream it belongs to: Blocks of block_size bytes but the last */
+} xzamd_resume_view;
+void xzamd_ctx_resume_(xzamd_ctx *c, xzamd_resume_view *v);
+xzamd_verify_report *xzamd_ctx_report_(xzamd_ctx *c);
+/* xzamd_stream_verify_device with the context's kept table, on behalf of an encode with XZAMD_F_VERIFY (xzamd_decode.c; the
+ * batch encoder refers to it weakly: a build of the host layer without the decoder has no verified encode) */
+int xzamd_verify_kept_(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size, void *stream);
+/* test hook: overwrite a field of record `record` of the kept table -- 0: upos = value, 1: kind = value, 2: state = value,
+ * 3: the whole model = 1024s */
+int xzamd_debug_resume_poke_(xzamd_ctx *c, uint32_t record, int field, uint32_t value);
+/* test hook: the 8 header words of a record of the kept table (hdr_out may be NULL), and how many records it has */
+int xzamd_debug_resume_peek_(xzamd_ctx *c, uint32_t record, uint32_t hdr_out[8], uint32_t *nrec_out);
 int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j);
 const char *xzamd_block_step_msg_(uint32_t step);
 

@@ -238,12 +238,24 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
  * through xzamd_stream_verify_device against d_in before the call returns: chunk-grammar scan, span-parallel decode, Checks,
  * comparison with the input.  Any defect returns XZAMD_DATA_ERROR, xzamd_last_error names the Block and the step,
  * xzamd_get_verify_report has the details, and *out_size is still set: the caller never gets XZAMD_OK for a Stream the device
- * decoder rejects or that differs from the input.  Nothing is rewritten; the caller decides what to do with the Stream.
+ * decoder rejects or that differs from the input.  Nothing is rewritten; the caller decides what to do with the Stream
+ * (xzamd_stream_verify_blocks_device names every bad Block, xzamd_stream_repair_device replaces them; XZAMD_F_REPAIR does both).
  * (Known at this version: a Block whose first piece is stored raw -- e.g. 512 KiB of random bytes in front of text -- can come
- * out with its first LZMA chunk lacking the properties byte, which every decoder rejects; XZAMD_F_VERIFY is what reports it.)
- * Either flag with XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS is XZAMD_OPTIONS_ERROR: there is no container to read. */
+ * out with its first LZMA chunk lacking the properties byte, which every decoder rejects; XZAMD_F_VERIFY is what reports it,
+ * XZAMD_F_REPAIR delivers a valid Stream for it.)
+ * Either flag with XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS is XZAMD_OPTIONS_ERROR: there is no container to read.
+ * XZAMD_F_REPAIR (implies XZAMD_F_VERIFY): VERIFIED AND REPAIRED ENCODE.  The verification is the per-Block one
+ * (xzamd_stream_verify_blocks_device); every Block it rejects is re-encoded from its slice of d_in and spliced into d_out as
+ * xzamd_stream_repair_device does, with the call's own options, before the call returns: XZAMD_OK, *out_size = the repaired size,
+ * binfo rewritten for the Blocks that moved, xzamd_get_repair_report says what happened, xzamd_get_verify_report describes the
+ * final, passing verification.  A Stream without a bad Block is byte for byte that of a call without the flag.
+ * XZAMD_F_REPAIR | XZAMD_F_BLOCKS_ONLY is allowed (binfo must then hold every Block: the Block table is read from it and from
+ * the Block Headers in d_out; the splice rewrites the bare Blocks and binfo).  XZAMD_F_REPAIR | XZAMD_F_SEGMENTS is
+ * XZAMD_OPTIONS_ERROR: the chunk chains of the single-Block Stream of lzma_stream_encoder are not Blocks; repairing them is out
+ * of scope at this version.  A call with XZAMD_F_REPAIR never defers its back end. */
 #define XZAMD_F_KEEP_RESUME 4u
 #define XZAMD_F_VERIFY 8u
+#define XZAMD_F_REPAIR 16u
 
 typedef struct {
 	uint64_t unpadded_size;      /* Index record field 1 (block_util.c:45-76) */
@@ -306,8 +318,50 @@ typedef struct {
 } xzamd_verify_report;
 int xzamd_stream_verify_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size,
 		xzamd_verify_report *report, void *stream);
-/* The report of the context's last verification (xzamd_stream_verify_device or an encode with XZAMD_F_VERIFY). */
+/* The report of the context's last verification (xzamd_stream_verify_device, xzamd_stream_verify_blocks_device, or an encode
+ * with XZAMD_F_VERIFY / XZAMD_F_REPAIR). */
 void xzamd_get_verify_report(const xzamd_ctx *ctx, xzamd_verify_report *out);
+
+/* PER-BLOCK VERIFICATION: xzamd_stream_verify_device that does not stop at the first defect.  A Block that fails a step is
+ * marked with that step and taken out of the later ones; the others go on.  block_steps receives one XZAMD_VSTEP_* per Block
+ * (XZAMD_VSTEP_NONE = good).  A Block Header that fails its CRC32 or disagrees with the Index makes its Block bad at step
+ * "grammar" (the Index gives its extent); a damaged Stream Header, Footer or Index fails the whole call as before
+ * (first_bad_block = UINT64_MAX).  The steps speak about the Stream: a verification unit reads its history from the original,
+ * so a Block that fails at "decode" or "check" goes through once more on its own (history = its own output) and that run decides
+ * -- a wrong original shows as "compare".  The comparison counts differing bytes per Block.  The report's first_bad_step /
+ * first_bad_block name the defect xzamd_stream_verify_device would have stopped at (steps in their order, the lowest Block of
+ * a step; a comparison defect names its Block here).  d_original may be NULL: grammar, decode and Check only.
+ * One Stream; the kept resume table is used when it fits, as by xzamd_stream_verify_device.
+ * XZAMD_OK: every Block good.  XZAMD_DATA_ERROR: some Block bad, block_steps filled in.  XZAMD_BUF_ERROR: steps_cap too small,
+ * *nblocks set. */
+int xzamd_stream_verify_blocks_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size,
+		const void *d_original, uint64_t original_size, uint8_t *block_steps, uint64_t steps_cap,
+		uint64_t *nblocks, xzamd_verify_report *report, void *stream);
+
+/* REPAIR: hand back a valid Stream for one the device decoder rejects, at the price of re-encoding the rejected Blocks only.
+ * 1. per-Block verdicts (above); none bad: XZAMD_OK, the Stream untouched.
+ * 2. every bad Block is re-encoded from its slice of the original (uncompressed offset and size from the Index), runs of
+ *    adjacent bad Blocks of equal size in one call of the batch encoder.  Rung 1: `opt` single-phase -- an explicit span size
+ *    of 256 KiB, every span starts with a state reset and the properties (an option set xzamd_options_check refuses that way,
+ *    i.e. the optimal parser with pb > 2: the fast parser with the same dict_size / lc / lp / pb / filters) -- and verified
+ *    again.  Rung 2, for what rung 1 leaves rejected: the stored form, uncompressed LZMA2 chunks with the filters dropped.
+ * 3. splice: every Block behind the first repaired one moves, Index and Stream Footer are rebuilt.  The Check kind is the
+ *    Stream's; the spliced Stream goes through the per-Block verification once more.
+ * All or nothing: on any error the xz_size bytes at d_xz are what they were.  XZAMD_BUF_ERROR: the repaired Stream needs
+ * *new_size > xz_cap bytes.  A kept resume table stays usable: the records of repaired Blocks become void. */
+typedef struct {
+	uint64_t blocks, blocks_bad, blocks_reencoded, blocks_stored;   /* reencoded: accepted from rung 1; stored: rung 2 */
+	uint64_t size_before, size_after;
+	uint32_t passes;             /* verification passes run (>= 1) */
+	float ms_repair;             /* wall time, verification passes included */
+	float ms_verify_passes, ms_reencode, ms_splice;      /* its parts */
+	uint32_t reserved_;
+} xzamd_repair_report;
+int xzamd_stream_repair_device(xzamd_ctx *ctx, void *d_xz, uint64_t xz_size, uint64_t xz_cap,
+		const void *d_original, uint64_t original_size, const xzamd_lzma_options *opt,
+		uint64_t *new_size, xzamd_repair_report *report, void *stream);
+/* The report of the context's last repair (xzamd_stream_repair_device or an encode with XZAMD_F_REPAIR). */
+void xzamd_get_repair_report(const xzamd_ctx *ctx, xzamd_repair_report *out);
 
 /* ---- whole .xz files: concatenated Streams, Stream Padding, file index, range decode ----
  * An .xz file is one or more Streams, each followed by Stream Padding (zero bytes, a multiple of four): what `xz -d`

@@ -21,6 +21,7 @@ F_BLOCKS_ONLY = 1
 F_SEGMENTS = 2
 F_KEEP_RESUME = 4
 F_VERIFY = 8
+F_REPAIR = 16
 VSTEPS = ("none", "grammar", "decode", "check", "compare")     # XZAMD_VSTEP_*
 NO_BLOCK = 0xFFFFFFFFFFFFFFFF
 BCJ_X86 = 4
@@ -58,6 +59,14 @@ class VerifyReport(C.Structure):
     _fields_ = [("units", C.c_uint64), ("blocks", C.c_uint64), ("records_used", C.c_uint64), ("first_bad_block", C.c_uint64),
                 ("mismatching_words", C.c_uint64), ("table_used", C.c_uint32), ("first_bad_step", C.c_uint32),
                 ("ms_verify", C.c_float), ("reserved_", C.c_uint32)]
+
+
+class RepairReport(C.Structure):
+    """xzamd_repair_report: what the last repair of a context did."""
+    _fields_ = [("blocks", C.c_uint64), ("blocks_bad", C.c_uint64), ("blocks_reencoded", C.c_uint64),
+                ("blocks_stored", C.c_uint64), ("size_before", C.c_uint64), ("size_after", C.c_uint64),
+                ("passes", C.c_uint32), ("ms_repair", C.c_float), ("ms_verify_passes", C.c_float),
+                ("ms_reencode", C.c_float), ("ms_splice", C.c_float), ("reserved_", C.c_uint32)]
 
 
 class BlockInfo(C.Structure):
@@ -146,6 +155,15 @@ def lib():
             l.xzamd_get_verify_report.argtypes = [C.c_void_p, C.POINTER(VerifyReport)]
             l.xzamd_debug_resume_poke_.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32]
             l.xzamd_debug_resume_peek_.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        if hasattr(l, "xzamd_stream_repair_device"):    # (an older library lacks the per-Block verification and the repair)
+            l.xzamd_stream_verify_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                            C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                            C.POINTER(VerifyReport), C.c_void_p]
+            l.xzamd_stream_repair_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                     C.POINTER(LzmaOptions), C.POINTER(C.c_uint64),
+                                                     C.POINTER(RepairReport), C.c_void_p]
+            l.xzamd_get_repair_report.restype = None
+            l.xzamd_get_repair_report.argtypes = [C.c_void_p, C.POINTER(RepairReport)]
         l.xzamd_debug_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         l.xzamd_trace_enable.argtypes = [C.c_void_p, C.c_uint32]
         l.xzamd_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -286,7 +304,7 @@ class Encoder:
         return s
 
     def encode(self, data, opts=None, preset=6, block_size=0, check=CHECK_CRC64,
-               span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0):
+               span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0, repair=False):
         """Encode a CUDA uint8 tensor into an .xz Stream (CUDA uint8 tensor).
 
         Returns (out_tensor_view, block_infos). Runs on torch's current stream.
@@ -295,6 +313,9 @@ class Encoder:
         verify: verified encode -- the finished Stream is decoded on the device, span-parallel with that table, and
         compared with `data` before the call returns; a defect raises XzAmdError with code 9 (`.stream` = the Stream
         as written, `verify_report()` = the details).  `flags`: further XZAMD_F_* bits.
+        repair: verified and repaired encode (XZAMD_F_REPAIR) -- every Block the device decoder rejects is re-encoded and
+        spliced in before the call returns; `repair_report()` says what happened, the block infos are those of the
+        repaired Stream.  Allowed with blocks_only.
 
         Every XzAmdError raised here carries `code` (the XZAMD_* value; it used to be None for encode failures) and
         `stream` (what was written: empty unless the failure is a verification defect).
@@ -323,7 +344,8 @@ class Encoder:
             cur.synchronize()
         rc = lib().xzamd_stream_encode_device(
             self._ctx, C.c_void_p(data.data_ptr()), n, bs, C.byref(opts), check,
-            (F_BLOCKS_ONLY if blocks_only else 0) | (F_VERIFY if verify else 0) | (F_KEEP_RESUME if keep_resume else 0) | flags,
+            (F_BLOCKS_ONLY if blocks_only else 0) | (F_VERIFY if verify else 0) | (F_KEEP_RESUME if keep_resume else 0)
+            | (F_REPAIR if repair else 0) | flags,
             C.c_void_p(out.data_ptr()), out.numel(),
             C.byref(out_size), binfo, max(nblocks, 1), C.byref(nb), C.c_void_p(stream))
         if rc != 0:
@@ -357,6 +379,59 @@ class Encoder:
         if rc != 0:
             raise XzAmdError(f"xzamd_stream_verify_device failed ({rc})" + self._detail(), rc)
         return self.verify_report()
+
+    def verify_blocks(self, xz, original=None):
+        """Per-Block verification of an .xz Stream (CUDA uint8 tensor), against `original` when given (else grammar,
+        decode and Check only): one step name of VSTEPS per Block, "none" = good.  Bad Blocks do not raise; a damaged
+        Stream Header, Footer or Index does.  `verify_report()` has the details."""
+        import torch
+        for t in (xz,) + ((original,) if original is not None else ()):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == xz.device
+        torch.cuda.current_stream(xz.device).synchronize()
+        f = lib().xzamd_stream_verify_blocks_device
+        nb = C.c_uint64(0)
+        args = (self._ctx, C.c_void_p(xz.data_ptr()), xz.numel(),
+                C.c_void_p(original.data_ptr()) if original is not None else None,
+                original.numel() if original is not None else 0)
+        rc = f(*args, None, 0, C.byref(nb), None, None)
+        if rc not in (0, 10):
+            raise XzAmdError(f"xzamd_stream_verify_blocks_device failed ({rc})" + self._detail(), rc)
+        steps = (C.c_uint8 * max(nb.value, 1))()
+        rc = f(*args, steps, nb.value, C.byref(nb), None, None)
+        if rc not in (0, 9):
+            raise XzAmdError(f"xzamd_stream_verify_blocks_device failed ({rc})" + self._detail(), rc)
+        if rc == 9 and not any(steps[: nb.value]):
+            raise XzAmdError("xzamd_stream_verify_blocks_device failed (9)" + self._detail(), rc)
+        return [VSTEPS[v] if v < len(VSTEPS) else str(v) for v in steps[: nb.value]]
+
+    def repair_report(self):
+        """The report of this context's last repair (`repair`, or an encode with repair=True) as a dict named like the
+        fields of xzamd_repair_report."""
+        r = RepairReport()
+        lib().xzamd_get_repair_report(self._ctx, C.byref(r))
+        return {n: getattr(r, n) for n, _ in RepairReport._fields_ if n != "reserved_"}
+
+    def repair(self, buf, size, original, opts=None, preset=6):
+        """Repair, in place, the .xz Stream in the first `size` bytes of the CUDA uint8 tensor `buf` (its capacity: the
+        whole tensor) against `original`: the Blocks the device decoder rejects are re-encoded with `opts` and spliced
+        in.  All or nothing: an XzAmdError (code 10 when `buf` is too small, with `.new_size` = what is needed) leaves
+        the Stream as it was.  Returns (view of the repaired Stream, report dict)."""
+        import torch
+        for t in (buf, original):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == buf.device
+        assert 0 <= size <= buf.numel()
+        if opts is None:
+            opts = preset_options(preset)
+        torch.cuda.current_stream(buf.device).synchronize()
+        ns = C.c_uint64(0)
+        rc = lib().xzamd_stream_repair_device(self._ctx, C.c_void_p(buf.data_ptr()), size, buf.numel(),
+                                              C.c_void_p(original.data_ptr()), original.numel(), C.byref(opts),
+                                              C.byref(ns), None, None)
+        if rc != 0:
+            err = XzAmdError(f"xzamd_stream_repair_device failed ({rc})" + self._detail(), rc)
+            err.new_size = ns.value
+            raise err
+        return buf[: ns.value], self.repair_report()
 
     def debug_resume_records(self):
         """Test instrumentation: records of the kept resume table (0: none kept)."""

@@ -264,7 +264,8 @@ typedef struct {
  * decode: history is the original; a full unit table is error 11); 2 = a unit at every chunk that resets the dictionary
  * (plain decode; once the table is full, further resets stay inside the last unit); 3 = verification decode with a resume
  * table (d_rec: nrec records of rec_stride bytes, sorted by Block then upos): a unit at the Block's first chunk and at every
- * chunk start whose Block offset is the upos of the Block's next record; a record that is not met there is error 13 */
+ * chunk start whose Block offset is the upos of the Block's next record; a record that is not met there is error 13; a Block
+ * whose records are all void (stored, or repaired) has the units of split 1 */
 int xzk_dec_scan(const uint8_t *d_xz, xzamd_dec_block *d_blocks, uint32_t nblocks, xzamd_dec_unit *d_units,
 		uint32_t units_cap, int split, const uint8_t *d_rec, uint32_t rec_stride, uint32_t nrec, void *stream);
 /* d_expected: one wavefront per unit, history read from it.  Else per_unit != 0: one wavefront per unit (units that start
@@ -275,6 +276,14 @@ int xzk_dec_units(const uint8_t *d_xz, const xzamd_dec_block *d_blocks, uint32_t
 		uint16_t *d_lit_pool, uint32_t waves, uint32_t *d_counter, uint32_t *d_block_err, int per_unit,
 		const uint8_t *d_rec, uint32_t rec_stride, void *stream);
 int xzk_dec_compare(const uint8_t *a, const uint8_t *b, uint64_t n, unsigned long long *d_mismatches, void *stream);
+/* Per-Block comparison (the collecting verification): d_counts[b] += bytes of Block b (d_blocks: upos, usize) that differ
+ * between d_out and d_expected.  One workgroup per tile of XZAMD_UNF_TILE bytes; d_tile_first (nblocks + 1, exclusive prefix
+ * sum of the tiles per Block, total_tiles last) as for xzk_dec_unfilter: a Block without tiles is not read.  d_counts must be
+ * zero on entry. */
+int xzk_dec_compare_blocks(const uint8_t *d_out, const uint8_t *d_expected, const xzamd_dec_block *d_blocks,
+		const uint32_t *d_tile_first, uint32_t nblocks, uint32_t total_tiles, unsigned long long *d_counts, void *stream);
+/* Resume table: every record of a Block b < nblocks with d_bad[b] != 0 becomes XZAMD_RK_VOID (a repaired Block) */
+int xzk_resume_void_blocks(uint8_t *d_table, uint32_t rec_stride, uint32_t nrec, const uint8_t *d_bad, uint32_t nblocks, void *stream);
 
 /* ---- inverse filters of the Block decoder (lzma_decode.hip) ----
  * The filters in front of LZMA2 of one Block, in the order of its Block Header: f[i] = filter id | parameter << 8

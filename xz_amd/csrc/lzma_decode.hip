@@ -59,10 +59,16 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
     // split 3: the Block's slice of the sorted records starts at the first record of a Block >= b; `r` is its cursor.  A
     // record is only ever COMPARED here (Block, upos) -- nothing of it becomes an address before a chunk start has met it.
     uint32_t r = 0, nrecs = 0;
+    bool self_units = false;
     if (split == 3) {
         uint32_t lo = 0, hi = nrec;
         while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (rec_hdr(rec_tab, rec_stride, mid)[0] < b) lo = mid + 1; else hi = mid; }
         r = lo;
+        // a Block all of whose records are void and that is coded all the same (a repaired Block: re-encoded single-phase)
+        // gets the units of split 1; a stored Block has no such chunk, so nothing changes for it
+        uint32_t q = r;
+        while (q < nrec && rec_hdr(rec_tab, rec_stride, q)[0] == b && (rec_hdr(rec_tab, rec_stride, q)[2] >> 24) == XZAMD_RK_VOID) ++q;
+        self_units = q > r && !(q < nrec && rec_hdr(rec_tab, rec_stride, q)[0] == b);
     }
     while (c < B.csize) {
         const uint32_t ctl = p[c];
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
                 need_props = false;
             }
             if (need_props) { err = DEC_NEED_PROPS; break; }
-            if (ctl >= 0xC0 && split == 1) starts_unit = true; // carries the properties and resets the state: self-contained
+            if (ctl >= 0xC0 && (split == 1 || self_units)) starts_unit = true; // carries the properties and resets the state: self-contained
             if (ctl >= 0xE0 && split == 2) starts_unit = true; // dictionary reset: nothing in front of it is referenced
         } else if (ctl == 0x01 || ctl == 0x02) {
             if (c + 3 > B.csize) { err = DEC_TRUNCATED; break; }
@@ -499,6 +505,63 @@ __global__ __launch_bounds__(256) void k_dec_compare(const uint8_t* __restrict__
         }
     }
     if (bad) atomicAdd(mismatches, (unsigned long long)bad);
+}
+
+// bytes of a 32-bit word that are not zero
+__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w)
+{
+    w |= w >> 4; w |= w >> 2; w |= w >> 1;
+    return (uint32_t)__popc(w & 0x01010101u);
+}
+
+// Per-Block verification: bytes of every Block that differ from the original, one 64-bit count per Block.  One workgroup
+// per tile of XZAMD_UNF_TILE bytes of a Block; tile_first (nblocks + 1, exclusive prefix sum) maps a tile to its Block as in
+// unf_locate, and a Block the host gives no tiles (one that failed an earlier step) is not read.  A Block starts at any
+// byte offset: the tile's head up to the next 16-byte boundary of the decoded bytes and its tail go byte by byte, the
+// interior in 16-byte loads (the original is read unaligned when it is not co-aligned).  The count is summed over the
+// wavefront on the DPP network; a wavefront that found differences issues one atomic.
+__global__ __launch_bounds__(256) void k_dec_compare_blocks(const uint8_t* __restrict__ out, const uint8_t* __restrict__ expected,
+        const xzamd_dec_block* __restrict__ blocks, const uint32_t* __restrict__ tile_first, uint32_t nblocks,
+        unsigned long long* __restrict__ counts)
+{
+    const uint32_t tile = blockIdx.x;
+    uint32_t lo = 0, hi = nblocks;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (tile_first[mid] <= tile) lo = mid; else hi = mid; }
+    const uint64_t usize = blocks[lo].usize;
+    const uint64_t p0 = (uint64_t)(tile - tile_first[lo]) * XZAMD_UNF_TILE;
+    if (tile < tile_first[lo] || tile >= tile_first[lo + 1] || p0 >= usize) return;     // (a table that does not cover the tile)
+    const uint32_t len = (uint32_t)(usize - p0 < XZAMD_UNF_TILE ? usize - p0 : XZAMD_UNF_TILE);
+    const uint8_t* a = out + blocks[lo].upos + p0;
+    const uint8_t* e = expected + blocks[lo].upos + p0;
+    const uint32_t t = threadIdx.x;
+    uint32_t head = (16u - (uint32_t)((uintptr_t)a & 15u)) & 15u;
+    if (head > len) head = len;
+    const uint32_t nvec = (len - head) / 16u, tail0 = head + nvec * 16u;
+    uint32_t bad = 0;
+    if (t < head) bad += a[t] != e[t];
+    if (t < len - tail0) bad += a[tail0 + t] != e[tail0 + t];
+    const uint4* a4 = reinterpret_cast<const uint4*>(a + head);
+    const bool co_aligned = ((uintptr_t)(e + head) & 15u) == 0;       // wave-uniform
+    for (uint32_t v = t; v < nvec; v += 256) {
+        const uint4 x = a4[v];
+        uint4 y;
+        if (co_aligned) y = reinterpret_cast<const uint4*>(e + head)[v];
+        else __builtin_memcpy(&y, e + head + 16u * v, 16);
+        const uint32_t d0 = x.x ^ y.x, d1 = x.y ^ y.y, d2 = x.z ^ y.z, d3 = x.w ^ y.w;
+        if (d0 | d1 | d2 | d3) bad += nonzero_bytes(d0) + nonzero_bytes(d1) + nonzero_bytes(d2) + nonzero_bytes(d3);
+    }
+    const uint32_t sum = wave_sum_dpp(bad);
+    if (sum != 0 && (t & 63u) == 0) atomicAdd(counts + lo, (unsigned long long)sum);
+}
+
+// Repair: the records of the Blocks flagged in `bad` (one byte per Block of the Stream) match nothing any more
+__global__ __launch_bounds__(256) void k_resume_void_blocks(uint8_t* __restrict__ tab, uint32_t stride, uint32_t nrec,
+        const uint8_t* __restrict__ bad, uint32_t nblocks)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nrec) return;
+    const uint32_t b = rec_hdr(tab, stride, r)[0];
+    if (b < nblocks && bad[b]) tab[(uint64_t)r * stride + XZAMD_RESUME_KIND_OFF] = (uint8_t)XZAMD_RK_VOID;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1002,6 +1065,23 @@ int xzk_dec_compare(const uint8_t* a, const uint8_t* b, uint64_t n, unsigned lon
     if (g > 65536) g = 65536;
     if (g == 0) g = 1;
     hipLaunchKernelGGL(k_dec_compare, dim3((uint32_t)g), dim3(256), 0, (hipStream_t)stream_, a, b, n, d_mismatches);
+    return (int)hipGetLastError();
+}
+
+int xzk_dec_compare_blocks(const uint8_t* d_out, const uint8_t* d_expected, const xzamd_dec_block* d_blocks,
+        const uint32_t* d_tile_first, uint32_t nblocks, uint32_t total_tiles, unsigned long long* d_counts, void* stream_)
+{
+    if (total_tiles == 0 || nblocks == 0) return 0;
+    hipLaunchKernelGGL(k_dec_compare_blocks, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream_, d_out, d_expected, d_blocks,
+            d_tile_first, nblocks, d_counts);
+    return (int)hipGetLastError();
+}
+
+int xzk_resume_void_blocks(uint8_t* d_table, uint32_t rec_stride, uint32_t nrec, const uint8_t* d_bad, uint32_t nblocks, void* stream_)
+{
+    if (nrec == 0 || nblocks == 0) return 0;
+    hipLaunchKernelGGL(k_resume_void_blocks, dim3((nrec + 255) / 256), dim3(256), 0, (hipStream_t)stream_, d_table, rec_stride, nrec,
+            d_bad, nblocks);
     return (int)hipGetLastError();
 }
 

@@ -92,6 +92,15 @@ static int fail_block_(xzamd_ctx *c, const xzamd_dec_job *j, uint64_t b, uint32_
 	return xzamd_ctx_fail_(c, XZAMD_DATA_ERROR, buf);
 }
 #define FAILB(b, vstep, msg) do { rc = fail_block_(c, j, (b), (vstep), (msg)); goto done; } while (0)
+/* ... in collect mode (j->steps): the Block is marked and the run goes on; the message and the report keep the first defect */
+static void mark_block_(xzamd_ctx *c, const xzamd_dec_job *j, uint64_t b, uint32_t vstep, const char *msg, int *any)
+{
+	if (j->steps[b] == XZAMD_VSTEP_NONE) j->steps[b] = (uint8_t)vstep;
+	if (!*any) (void)fail_block_(c, j, b, vstep, msg);
+	*any = 1;
+}
+#define BADB(b, vstep, msg) do { if (!j->steps) FAILB((b), (vstep), (msg)); mark_block_(c, j, (b), (vstep), (msg), &any_bad); } while (0)
+#define IS_BAD(b) (j->steps && j->steps[b] != XZAMD_VSTEP_NONE)
 
 /* The device part of a decode: the Blocks of j->hb (parsed and validated: xzb_block) through unit scan, LZMA2 decode,
  * inverse filters, Checks (per group of Blocks = per Stream) and the comparison with the original. */
@@ -114,11 +123,14 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 	void *d_chains = NULL, *d_tiles = NULL, *d_t0 = NULL, *d_t1 = NULL, *d_filt = NULL, *d_tsum = NULL, *d_tcarry = NULL;
 	uint32_t max_nf = 0;
 	int any_filtered = 0, any_plain = 0;
+	int any_bad = 0;                   /* collect mode: some Block is marked */
+	void *d_cmp = NULL;
 	uint64_t utotal = 0, max_usize = 0;
 	if (j->report) j->report->blocks = nb;
 	if (nb == 0) return XZAMD_OK;
 	if (nb >= (1ull << 31)) return xzamd_ctx_fail_(c, XZAMD_OPTIONS_ERROR, "too many Blocks for the device decoder");
 	for (uint64_t b = 0; b < nb; ++b) {
+		if (IS_BAD(b)) any_bad = 1;        /* (marked by the caller, who has reported it) */
 		if (hc[b].n) { any_filtered = 1; if (hc[b].n > max_nf) max_nf = hc[b].n; } else any_plain = 1;
 		utotal += hb[b].usize;
 		if (hb[b].usize > max_usize) max_usize = hb[b].usize;
@@ -136,8 +148,9 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 		 * dictionary reset -- nothing in front of one can be referenced, so the units of a Block decode side by side with
 		 * the output itself as history.  The unit count of a Block is data: the table holds usize / 4096 + 8 per Block,
 		 * and in the plain mode a Block with more resets keeps the rest inside its last unit. */
-		const int with_table = d_expected != NULL && j->allow_split && j->d_rec != NULL && j->nrec != 0;
-		int split = d_expected != NULL ? (j->allow_split ? (with_table ? 3 : 1) : 0) : 2;
+		const int verif = d_expected != NULL && !j->plain_history;      /* the units read their history from the original */
+		const int with_table = verif && j->allow_split && j->d_rec != NULL && j->nrec != 0;
+		int split = verif ? (j->allow_split ? (with_table ? 3 : 1) : 0) : 2;
 		uint32_t units_cap = split ? (uint32_t)(max_usize / 4096 + 8) : 1;
 		if ((uint64_t)units_cap * nb > (1ull << 27)) { split = 0; units_cap = 1; }
 		uint32_t waves = xzamd_ctx_wave_slots_(c);
@@ -197,9 +210,12 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 		uint64_t recs_used = 0;
 		int overflow = 0;
 		for (uint64_t b = 0; b < nb; ++b) {
-			if (hb[b].error == 11) overflow = 1;
-			else if (hb[b].error == 13) FAILB(b, XZAMD_VSTEP_GRAMMAR, "a resume record names a span start that is no LZMA2 chunk start");
-			else if (hb[b].error) FAILB(b, XZAMD_VSTEP_GRAMMAR, "LZMA2 chunk grammar");
+			if (!IS_BAD(b)) {                         /* (bad already: its header -- the Block has no chunk chain to speak of) */
+				if (hb[b].error == 11) overflow = 1;
+				else if (hb[b].error == 13) BADB(b, XZAMD_VSTEP_GRAMMAR, "a resume record names a span start that is no LZMA2 chunk start");
+				else if (hb[b].error) BADB(b, XZAMD_VSTEP_GRAMMAR, "LZMA2 chunk grammar");
+			}
+			if (IS_BAD(b)) hb[b].nunits = 0;          /* out of the decode: its units are not listed */
 			unit_first[b] = total_units;
 			total_units += hb[b].nunits;
 			recs_used += hb[b].nrecs;
@@ -209,6 +225,7 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			/* more state resets than anticipated: one unit per Block, compared afterwards all the same */
 			xzk_free(d_units); d_units = NULL;
 			for (uint64_t b = 0; b < nb; ++b) { hb[b].error = 0; hb[b].nunits = 0; }
+			/* (collect mode: the Blocks the first scan marked stay marked -- their defect does not depend on the split) */
 			split = 0; units_cap = 1;
 			goto rescan;
 		}
@@ -237,7 +254,7 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 		HIPD(xzk_d2h(h_err, d_berr, 4 * nb, st) || xzk_sync(st), "decode");
 		reads_(j, 1);
 		for (uint64_t b = 0; b < nb; ++b)
-			if (h_err[b]) FAILB(b, XZAMD_VSTEP_DECODE, "LZMA2 data (range coder / distances / chunk sizes)");
+			if (h_err[b] && !IS_BAD(b)) BADB(b, XZAMD_VSTEP_DECODE, "LZMA2 data (range coder / distances / chunk sizes)");
 		if (any_filtered) {
 			/* inverse stages, the filter next to LZMA2 first; an unfiltered Block of a mixed Stream is copied in stage 0 */
 			xzamd_unf_args ua;
@@ -252,6 +269,7 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 				uint32_t kinds = 0;
 				for (uint64_t b = 0; b < nb; ++b) {
 					tile_first[b] = (uint32_t)tiles;
+					if (IS_BAD(b)) continue;
 					if (hc[b].n > k || (hc[b].n == 0 && k == 0)) {
 						const uint32_t kind = hc[b].n ? hc[b].f[hc[b].n - 1 - k] & 0xFFu : 0u;
 						tiles += (hb[b].usize + XZAMD_UNF_TILE - 1) / XZAMD_UNF_TILE;
@@ -344,16 +362,42 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			const int check = j->groups[g].check;
 			for (uint64_t b = j->groups[g].first; b < j->groups[g].first + j->groups[g].count; ++b) {
 				const uint8_t *sb = j->stored + XZAMD_HDR_CHECK_BYTES * b;
+				if (IS_BAD(b)) continue;
 				if (check == XZAMD_CHECK_CRC32 || check == XZAMD_CHECK_CRC64) {
 					uint64_t sv = 0;
 					for (uint32_t i = 0; i < (check == XZAMD_CHECK_CRC32 ? 4u : 8u); ++i) sv |= (uint64_t)sb[i] << (8 * i);
-					if (h_crc[b] != sv) FAILB(b, XZAMD_VSTEP_CHECK, "Block Check mismatch");
+					if (h_crc[b] != sv) BADB(b, XZAMD_VSTEP_CHECK, "Block Check mismatch");
 				} else if (check == XZAMD_CHECK_SHA256) {
-					if (memcmp(h_sha + 32 * b, sb, 32) != 0) FAILB(b, XZAMD_VSTEP_CHECK, "Block Check mismatch (SHA-256)");
+					if (memcmp(h_sha + 32 * b, sb, 32) != 0) BADB(b, XZAMD_VSTEP_CHECK, "Block Check mismatch (SHA-256)");
 				}
 			}
 		}
-		if (d_expected) {
+		if (d_expected && j->steps) {
+			/* collect mode: one count of differing bytes per Block that got this far (k_dec_compare_blocks); the global word
+			 * count of the plain path only when that path would have reached its comparison */
+			uint64_t tiles = 0;
+			unsigned long long mm = 0;
+			for (uint64_t b = 0; b < nb; ++b) {
+				tile_first[b] = (uint32_t)tiles;
+				if (!IS_BAD(b)) tiles += (hb[b].usize + XZAMD_UNF_TILE - 1) / XZAMD_UNF_TILE;
+			}
+			tile_first[nb] = (uint32_t)tiles;
+			if (tiles >= (1ull << 31)) FAILD(XZAMD_OPTIONS_ERROR, "Stream too large for the per-Block comparison");
+			unsigned long long *h_cnt = (unsigned long long *)h_crc;      /* (the Checks have been looked at) */
+			HIPD(xzk_malloc(&d_cmp, 12 * nb + 16), "hipMalloc");
+			uint32_t *d_tf = (uint32_t *)((uint8_t *)d_cmp + 8 * nb);
+			HIPD(xzk_memset(d_cmp, 0, 8 * nb, st) || xzk_h2d(d_tf, tile_first, 4 * (nb + 1), st), "h2d tiles");
+			HIPD(xzk_dec_compare_blocks(d_out, d_expected, (const xzamd_dec_block *)d_blocks, d_tf, nbk, (uint32_t)tiles,
+					(unsigned long long *)d_cmp, st), "compare launch");
+			launches_(j, 1);
+			if (!any_bad) { HIPD(xzk_dec_compare(d_out, d_expected, utotal, d_mism, st), "compare launch"); launches_(j, 1); }
+			HIPD(xzk_d2h(h_cnt, d_cmp, 8 * nb, st) || xzk_d2h(&mm, d_mism, 8, st) || xzk_sync(st), "d2h compare");
+			reads_(j, 1);
+			if (mismatches) *mismatches = mm;
+			if (j->report) j->report->mismatching_words = mm;
+			for (uint64_t b = 0; b < nb; ++b)
+				if (!IS_BAD(b) && h_cnt[b]) BADB(b, XZAMD_VSTEP_COMPARE, "decoded bytes differ from the original");
+		} else if (d_expected) {
 			unsigned long long mm = 0;
 			HIPD(xzk_dec_compare(d_out, d_expected, utotal, d_mism, st), "compare launch");
 			launches_(j, 1);
@@ -364,8 +408,10 @@ int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j)
 			if (mm) FAILB(UINT64_MAX, XZAMD_VSTEP_COMPARE, "decoded bytes differ from the original");
 		}
 	}
+	if (any_bad) rc = XZAMD_DATA_ERROR;       /* (message and report: the first defect, set when it was marked) */
 done:
 	xzk_sync(st);
+	if (d_cmp) xzk_free(d_cmp);
 	if (d_blocks) xzk_free(d_blocks);
 	if (d_units) xzk_free(d_units);
 	if (d_first) xzk_free(d_first);
@@ -579,6 +625,252 @@ int xzamd_stream_verify_device(xzamd_ctx *c, const void *d_xz, uint64_t xz_size,
 int xzamd_verify_kept_(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size, void *stream)
 {
 	return xzamd_stream_verify_device(c, d_xz, xz_size, d_original, original_size, NULL, stream);
+}
+
+/* ---- per-Block verification (DESIGN.md 3.6 "Repair") ---- */
+
+/* The framing of stream_decode_ without its Blocks: Stream Header, Footer, Index -> the Index records as the table the
+ * Block Header kernel reads.  Same checks, same codes; what the Blocks themselves hold is the collecting run's business. */
+int xzamd_stream_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, xzamd_hdr_rec **recs_out, uint64_t *nb_out, int *check_out,
+		void *st)
+{
+	static const uint8_t magic[6] = { 0xFD, '7', 'z', 'X', 'Z', 0x00 };
+	static const uint8_t check_sizes[16] = { 0, 4, 4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64 };
+	int rc = XZAMD_OK;
+	uint8_t hf[24];
+	uint8_t *index = NULL;
+	xzamd_hdr_rec *recs = NULL;
+	*recs_out = NULL; *nb_out = 0; *check_out = 0;
+	if (xz_size < 32 || (xz_size & 3))
+		FAILD(FORMAT_ERROR, "not an .xz Stream (size)");
+	HIPD(xzk_d2h(hf, d_xz, 12, st) || xzk_d2h(hf + 12, d_xz + xz_size - 12, 12, st) || xzk_sync(st), "d2h stream flags");
+	if (memcmp(hf, magic, 6) != 0 || hf[22] != 'Y' || hf[23] != 'Z')
+		FAILD(FORMAT_ERROR, "bad magic bytes");
+	if (rd32(hf + 8) != xzamd_crc32_host_(hf + 6, 2) || rd32(hf + 12) != xzamd_crc32_host_(hf + 16, 6))
+		FAILD(XZAMD_DATA_ERROR, "Stream Header / Footer CRC32");
+	if (hf[6] != 0 || (hf[7] & 0xF0) || hf[6] != hf[20] || hf[7] != hf[21])
+		FAILD(XZAMD_OPTIONS_ERROR, "unsupported or inconsistent Stream Flags");
+	const int check = hf[7] & 0x0F;
+	if (check != XZAMD_CHECK_NONE && check != XZAMD_CHECK_CRC32 && check != XZAMD_CHECK_CRC64 && check != XZAMD_CHECK_SHA256)
+		FAILD(XZAMD_UNSUPPORTED_CHECK, "Check id the device decoder cannot verify");
+	const uint32_t csz = check_sizes[check];
+	const uint64_t index_size = ((uint64_t)rd32(hf + 16) + 1) * 4;
+	if (index_size + 24 > xz_size)
+		FAILD(XZAMD_DATA_ERROR, "Backward Size");
+	const uint64_t index_at = xz_size - 12 - index_size;
+	index = (uint8_t *)malloc(index_size);
+	if (!index) FAILD(XZAMD_MEM_ERROR, "malloc");
+	HIPD(xzk_d2h(index, d_xz + index_at, index_size, st) || xzk_sync(st), "d2h index");
+	if (index[0] != 0x00 || rd32(index + index_size - 4) != xzamd_crc32_host_(index, index_size - 4))
+		FAILD(XZAMD_DATA_ERROR, "Index indicator / CRC32");
+	uint64_t ip = 1, nb = 0;
+	if (xzb_vli(index, index_size - 4, &ip, &nb) || nb > (index_size / 2))
+		FAILD(XZAMD_DATA_ERROR, "Index record count");
+	if (nb >= (1ull << 31)) FAILD(XZAMD_OPTIONS_ERROR, "too many Blocks for the device decoder");
+	recs = (xzamd_hdr_rec *)calloc(nb ? nb : 1, sizeof(*recs));
+	if (!recs) FAILD(XZAMD_MEM_ERROR, "malloc");
+	uint64_t pos = 12, utotal = 0;
+	for (uint64_t b = 0; b < nb; ++b) {
+		uint64_t unpadded = 0, usize = 0;
+		if (xzb_vli(index, index_size - 4, &ip, &unpadded) || xzb_vli(index, index_size - 4, &ip, &usize)
+				|| unpadded < 5 + csz || unpadded > (1ull << 62) || usize > (1ull << 62))
+			FAILD(XZAMD_DATA_ERROR, "Index record");
+		const uint64_t padded = (unpadded + 3) & ~3ull;
+		if (padded > index_at - pos)
+			FAILD(XZAMD_DATA_ERROR, "Block beyond the Index");
+		recs[b].hpos = pos; recs[b].unpadded = unpadded; recs[b].usize = usize;
+		recs[b].end = index_at; recs[b].upos = utotal; recs[b].csz = csz;
+		pos += padded;
+		utotal += usize;
+	}
+	for (; ip < index_size - 4; ++ip)
+		if (index[ip] != 0) FAILD(XZAMD_DATA_ERROR, "Index Padding");
+	if (pos != index_at)
+		FAILD(XZAMD_DATA_ERROR, "Blocks do not end where the Index starts");
+	*recs_out = recs; recs = NULL;
+	*nb_out = nb; *check_out = check;
+done:
+	free(index); free(recs);
+	return rc;
+}
+
+int xzamd_verify_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, const xzamd_hdr_rec *recs, uint64_t nb, int check,
+		const uint8_t *d_original, uint64_t original_size, int mode, uint8_t *steps, xzamd_verify_report *rp, void *st)
+{
+	int rc = XZAMD_OK;
+	void *d_recs = NULL, *d_table = NULL, *d_tmp = NULL;
+	uint8_t *h_table = NULL;
+	xzamd_dec_block *hb = NULL;
+	xzamd_dec_chain *hc = NULL;
+	uint8_t *stored = NULL;
+	xzamd_dec_block *hb2 = NULL;     /* the second run: Blocks that failed with the original as history */
+	xzamd_dec_chain *hc2 = NULL;
+	uint8_t *stored2 = NULL, *steps2 = NULL;
+	uint64_t utotal = 0;
+	memset(steps, 0, nb);
+	if (rp) rp->blocks = nb;
+	if (nb == 0) return XZAMD_OK;
+	for (uint64_t b = 0; b < nb; ++b) utotal += recs[b].usize;
+	if (d_original && original_size != utotal) {
+		if (rp && rp->first_bad_step == XZAMD_VSTEP_NONE) rp->first_bad_step = XZAMD_VSTEP_COMPARE;
+		return xzamd_ctx_fail_(c, XZAMD_DATA_ERROR, "the Stream's uncompressed size differs from the size of the original");
+	}
+	const uint64_t tbytes = XZAMD_HDR_TABLE_BYTES(nb);
+	hb = (xzamd_dec_block *)calloc(nb, sizeof(*hb));
+	hc = (xzamd_dec_chain *)calloc(nb, sizeof(*hc));
+	stored = (uint8_t *)calloc(nb, XZAMD_HDR_CHECK_BYTES);
+	h_table = (uint8_t *)malloc(tbytes);
+	if (!hb || !hc || !stored || !h_table) FAILD(XZAMD_MEM_ERROR, "malloc");
+	/* every Block Header, the sizes against the table, Block Padding, the stored Check: one thread per Block */
+	HIPD(xzk_malloc(&d_recs, nb * sizeof(*recs)) || xzk_malloc(&d_table, tbytes), "hipMalloc");
+	HIPD(xzk_h2d(d_recs, recs, nb * sizeof(*recs), st)
+			|| xzk_dec_headers(d_xz, xz_size, (const xzamd_hdr_rec *)d_recs, (uint32_t)nb, d_table, st)
+			|| xzk_d2h(h_table, d_table, tbytes, st) || xzk_sync(st), "Block Header kernel");
+	{
+		const uint8_t *p = h_table;
+		memcpy(hb, p, nb * sizeof(*hb)); p += nb * sizeof(*hb);
+		memcpy(hc, p, nb * sizeof(*hc)); p += nb * sizeof(*hc);
+		memcpy(stored, p, nb * XZAMD_HDR_CHECK_BYTES); p += nb * XZAMD_HDR_CHECK_BYTES;
+		const xzamd_hdr_err *he = (const xzamd_hdr_err *)p;
+		for (uint64_t b = 0; b < nb; ++b) {
+			if (!he[b].code) continue;
+			/* a Block whose header cannot be read: the table still gives its extent and its uncompressed size.  It takes no
+			 * part in the run (no chunk chain, no filters) */
+			char buf[160];
+			steps[b] = XZAMD_VSTEP_GRAMMAR;
+			if (rp && rp->first_bad_step == XZAMD_VSTEP_NONE) {
+				rp->first_bad_step = XZAMD_VSTEP_GRAMMAR;
+				rp->first_bad_block = b;
+				snprintf(buf, sizeof(buf), "Block %llu: %s", (unsigned long long)b, xzamd_block_step_msg_(he[b].step));
+				(void)xzamd_ctx_fail_(c, XZAMD_DATA_ERROR, buf);
+			}
+			hb[b].cpos = recs[b].hpos; hb[b].csize = 0; hb[b].upos = recs[b].upos; hb[b].usize = recs[b].usize;
+			hb[b].dict_size = 0; hb[b].nunits = 0; hb[b].error = 0; hb[b].nrecs = 0;
+			memset(&hc[b], 0, sizeof(hc[b]));
+			if (recs[b].usize >= (1ull << 31)) FAILD(XZAMD_OPTIONS_ERROR, "Block too large for the device decoder");
+		}
+	}
+	HIPD(xzk_malloc(&d_tmp, utotal + 16), "hipMalloc (verification output)");
+	{
+		const xzamd_dec_group group = { 0, nb, check };
+		xzamd_dec_job job;
+		xzamd_resume_view tab;
+		memset(&job, 0, sizeof(job));
+		job.d_xz = d_xz; job.d_out = (uint8_t *)d_tmp; job.d_expected = d_original;
+		job.nb = nb; job.hb = hb; job.hc = hc; job.stored = stored;
+		job.groups = &group; job.ngroups = 1;
+		/* (the forward filters of the span-parallel history read the original in aligned words) */
+		job.allow_split = ((uintptr_t)d_original & 15) == 0;
+		job.report = rp;
+		job.steps = steps;
+		xzamd_ctx_resume_(c, &tab);
+		if ((mode & XZAMD_VT_KEPT) && tab.d_rec && tab.nrec && d_original) {
+			/* the kept table fits under the rule of xzamd_stream_verify_device */
+			int fits = nb == tab.nblocks && utotal == tab.in_size;
+			for (uint64_t b = 0; fits && b < nb; ++b) {
+				const uint64_t left = tab.in_size - b * tab.block_size;
+				fits = hb[b].usize == (left < tab.block_size ? left : tab.block_size);
+			}
+			if (fits) { job.d_rec = tab.d_rec; job.rec_stride = tab.stride; job.nrec = tab.nrec; }
+		}
+		rc = xzamd_dec_run_(c, st, &job);
+		if (rc == XZAMD_DATA_ERROR && d_original && (mode & XZAMD_VT_PRECISE)) {
+			/* The verdicts speak about the STREAM.  A verification unit reads its history from the original, so a wrong
+			 * original makes a unit fail, or decode other bytes, as surely as wrong LZMA2 data does.  The Blocks that failed
+			 * at "decode" or "check" go through once more on their own -- history = their own output, units at dictionary
+			 * resets -- and that run decides: a sound Block of a Stream whose original differs ends at "compare". */
+			uint64_t n2 = 0;
+			for (uint64_t b = 0; b < nb; ++b) n2 += steps[b] == XZAMD_VSTEP_DECODE || steps[b] == XZAMD_VSTEP_CHECK;
+			if (n2) {
+				hb2 = (xzamd_dec_block *)calloc(n2, sizeof(*hb2));
+				hc2 = (xzamd_dec_chain *)calloc(n2, sizeof(*hc2));
+				stored2 = (uint8_t *)calloc(n2, XZAMD_HDR_CHECK_BYTES);
+				steps2 = (uint8_t *)calloc(n2, 1);
+				if (!hb2 || !hc2 || !stored2 || !steps2) FAILD(XZAMD_MEM_ERROR, "malloc");
+			}
+			/* one run of ADJACENT such Blocks per call: the Checks of a group of Blocks are taken over one stretch of the output */
+			for (uint64_t b0 = 0; b0 < nb && n2; ) {
+				if (steps[b0] != XZAMD_VSTEP_DECODE && steps[b0] != XZAMD_VSTEP_CHECK) { ++b0; continue; }
+				uint64_t n = 0;
+				while (b0 + n < nb && (steps[b0 + n] == XZAMD_VSTEP_DECODE || steps[b0 + n] == XZAMD_VSTEP_CHECK)) {
+					hb2[n] = hb[b0 + n]; hb2[n].nunits = 0; hb2[n].error = 0; hb2[n].nrecs = 0;
+					hc2[n] = hc[b0 + n];
+					memcpy(stored2 + XZAMD_HDR_CHECK_BYTES * n, stored + XZAMD_HDR_CHECK_BYTES * (b0 + n), XZAMD_HDR_CHECK_BYTES);
+					steps2[n] = XZAMD_VSTEP_NONE;
+					++n;
+				}
+				const xzamd_dec_group group2 = { 0, n, check };
+				xzamd_dec_job job2 = job;
+				job2.nb = n; job2.hb = hb2; job2.hc = hc2; job2.stored = stored2; job2.groups = &group2;
+				job2.d_rec = NULL; job2.nrec = 0; job2.plain_history = 1;
+				job2.report = NULL; job2.steps = steps2;
+				rc = xzamd_dec_run_(c, st, &job2);
+				if (rc != XZAMD_OK && rc != XZAMD_DATA_ERROR) goto done;
+				for (uint64_t i = 0; i < n; ++i) steps[b0 + i] = steps2[i];
+				b0 += n;
+			}
+			rc = XZAMD_OK;
+			for (uint64_t b = 0; b < nb; ++b) if (steps[b] != XZAMD_VSTEP_NONE) rc = XZAMD_DATA_ERROR;
+			/* what a run that stops at the first defect reports: the steps in their order, the lowest Block of a step */
+			static const char *const what[5] = { "", "container framing / LZMA2 chunk grammar", "LZMA2 data (range coder / distances / chunk sizes)",
+				"Block Check mismatch", "decoded bytes differ from the original" };
+			if (rp) { rp->first_bad_step = XZAMD_VSTEP_NONE; rp->first_bad_block = UINT64_MAX; }
+			for (uint32_t v = XZAMD_VSTEP_GRAMMAR; v <= XZAMD_VSTEP_COMPARE && rc == XZAMD_DATA_ERROR; ++v) {
+				uint64_t b = 0;
+				while (b < nb && steps[b] != v) ++b;
+				if (b == nb) continue;
+				char buf[160];
+				snprintf(buf, sizeof(buf), "Block %llu: %s", (unsigned long long)b, what[v]);
+				(void)xzamd_ctx_fail_(c, XZAMD_DATA_ERROR, buf);
+				if (rp) { rp->first_bad_step = v; rp->first_bad_block = b; }
+				break;
+			}
+		}
+	}
+done:
+	xzk_sync(st);
+	if (d_recs) xzk_free(d_recs);
+	if (d_table) xzk_free(d_table);
+	if (d_tmp) xzk_free(d_tmp);
+	free(h_table); free(hb); free(hc); free(stored);
+	free(hb2); free(hc2); free(stored2); free(steps2);
+	return rc;
+}
+
+int xzamd_stream_verify_blocks_device(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size,
+		uint8_t *block_steps, uint64_t steps_cap, uint64_t *nblocks, xzamd_verify_report *report, void *stream)
+{
+	if (!c || !d_xz || (!d_original && original_size) || (!block_steps && steps_cap))
+		return XZAMD_PROG_ERROR;
+	xzamd_verify_report *rp = xzamd_ctx_report_(c);
+	void *st = stream ? stream : xzamd_ctx_stream_(c);
+	struct timespec t0, t1;
+	xzamd_hdr_rec *recs = NULL;
+	uint64_t nb = 0;
+	int check = 0, rc;
+	clock_gettime(CLOCK_MONOTONIC, &t0);
+	memset(rp, 0, sizeof(*rp));
+	rp->first_bad_block = UINT64_MAX;
+	if (nblocks) *nblocks = 0;
+	if (report) *report = *rp;
+	if (xzk_set_device(xzamd_ctx_device(c)))
+		return xzamd_ctx_fail_(c, XZAMD_DEVICE_ERROR, "hipSetDevice");
+	rc = xzamd_stream_table_(c, (const uint8_t *)d_xz, xz_size, &recs, &nb, &check, st);
+	if (rc == XZAMD_OK) {
+		if (nblocks) *nblocks = nb;
+		if (nb > steps_cap) rc = xzamd_ctx_fail_(c, XZAMD_BUF_ERROR, "block_steps too small");
+	}
+	if (rc == XZAMD_OK)
+		rc = xzamd_verify_table_(c, (const uint8_t *)d_xz, xz_size, recs, nb, check, (const uint8_t *)d_original, original_size,
+				XZAMD_VT_KEPT | XZAMD_VT_PRECISE, block_steps, rp, st);
+	/* a defect of the container: no Block to name */
+	if ((rc == XZAMD_DATA_ERROR || rc == FORMAT_ERROR) && rp->first_bad_step == XZAMD_VSTEP_NONE)
+		rp->first_bad_step = XZAMD_VSTEP_GRAMMAR;
+	free(recs);
+	clock_gettime(CLOCK_MONOTONIC, &t1);
+	rp->ms_verify = (float)((double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6);
+	if (report) *report = *rp;
+	return rc;
 }
 
 void xzamd_get_verify_report(const xzamd_ctx *c, xzamd_verify_report *out)

@@ -73,6 +73,7 @@ typedef struct {
 	call_knobs k;
 	int check, whole, filtered, pipelined, defer, seeds_early;
 	int resume, verify;          /* XZAMD_F_KEEP_RESUME / _VERIFY on a two-phase encode: resume records are exported; verify the Stream */
+	int repair;                  /* XZAMD_F_REPAIR: the verification is the per-Block one, rejected Blocks are replaced */
 	uint32_t rec_done;           /* resume records of the batches that are through their back end */
 	uint8_t dbyte;
 	void *st, *stb;              /* front-end stream (the caller's), back-end stream (the second one when pipelined) */
@@ -110,6 +111,7 @@ struct xzamd_ctx {
 	dbuf resume_tab;
 	struct { int valid; uint32_t stride, nrec; uint64_t nblocks, block_size, in_size; } resume;
 	xzamd_verify_report report;                                    /* of the last verification */
+	xzamd_repair_report repair;                                    /* of the last repair */
 	/* pinned host buffers */
 	dbuf h_span_bytes, h_block_crc, h_segs, h_lits, h_span_tab, h_span_cnt[2], h_enc_tab[2], h_enc_cnt[2], h_err[2];
 	void *evp[2][EV_COUNT];
@@ -349,6 +351,30 @@ extern int xzk_resume_export(const xzamd_span_args *a, uint32_t nblocks, uint32_
 		uint32_t rec_cap, void *stream) __attribute__((weak));
 extern int xzamd_verify_kept_(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, const void *d_original, uint64_t original_size,
 		void *stream) __attribute__((weak));
+/* ... and the repair (xzamd_repair.c): without it XZAMD_F_REPAIR is XZAMD_OPTIONS_ERROR */
+extern int xzamd_repair_encoded_(xzamd_ctx *c, void *d_out, uint64_t size, uint64_t cap, const void *d_in, uint64_t in_size,
+		uint64_t block_size, const xzamd_lzma_options *opt, int check, int framed, xzamd_block_info *binfo, uint64_t binfo_cap,
+		uint64_t nblocks, uint64_t *new_size, void *stream) __attribute__((weak));
+xzamd_repair_report *xzamd_ctx_repair_report_(xzamd_ctx *c) { return &c->repair; }
+/* A repair re-encodes Blocks on the context of the call it repairs: the kept table leaves the context meanwhile (the
+ * re-encode would free it), the stats of the repaired call come back afterwards */
+void xzamd_ctx_save_(xzamd_ctx *c, xzamd_ctx_saved *s)
+{
+	s->tab = c->resume_tab.p; s->tab_cap = c->resume_tab.cap;
+	s->valid = c->resume.valid; s->stride = c->resume.stride; s->nrec = c->resume.nrec;
+	s->nblocks = c->resume.nblocks; s->block_size = c->resume.block_size; s->in_size = c->resume.in_size;
+	s->stats = c->stats;
+	c->resume_tab.p = NULL; c->resume_tab.cap = 0;
+	c->resume.valid = 0;
+}
+void xzamd_ctx_restore_(xzamd_ctx *c, const xzamd_ctx_saved *s)
+{
+	if (c->resume_tab.p) xzk_free(c->resume_tab.p);
+	c->resume_tab.p = s->tab; c->resume_tab.cap = s->tab_cap;
+	c->resume.valid = s->valid; c->resume.stride = s->stride; c->resume.nrec = s->nrec;
+	c->resume.nblocks = s->nblocks; c->resume.block_size = s->block_size; c->resume.in_size = s->in_size;
+	c->stats = s->stats;
+}
 void xzamd_get_stats(const xzamd_ctx *c, xzamd_stats *out) { *out = c->stats; }
 const char *xzamd_version(void) { return "xz_amd 0.1 (gfx950)"; }
 
@@ -476,8 +502,15 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		flags |= XZAMD_F_BLOCKS_ONLY;
 	if ((unsigned)check > 15)
 		return fail(c, XZAMD_PROG_ERROR, "check id out of range", 0);
-	if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && (flags & XZAMD_F_BLOCKS_ONLY))
+	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_SEGMENTS))
+		return fail(c, XZAMD_OPTIONS_ERROR, "repair: Blocks only, not the chunk chains of XZAMD_F_SEGMENTS", 0);
+	if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && (flags & XZAMD_F_BLOCKS_ONLY) && !(flags & XZAMD_F_REPAIR))
 		return fail(c, XZAMD_OPTIONS_ERROR, "keep_resume / verify need a whole Stream: not with XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS", 0);
+	if (flags & XZAMD_F_REPAIR) {
+		if (!xzamd_repair_encoded_)
+			return fail(c, XZAMD_OPTIONS_ERROR, "repair: this build has no repair unit", 0);
+		flags |= XZAMD_F_VERIFY;
+	}
 	if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && (!xzk_resume_export || !xzamd_verify_kept_))
 		return fail(c, XZAMD_OPTIONS_ERROR, "keep_resume / verify: this build has no resume export or no device decoder", 0);
 	if ((flags & XZAMD_F_SEGMENTS) && (check == XZAMD_CHECK_SHA256 || opt->bcj != 0))
@@ -520,6 +553,8 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		return fail(c, XZAMD_OPTIONS_ERROR, "block_size too large for one device batch", 0);
 
 	const uint64_t total_blocks = (in_size + block_size - 1) / block_size;
+	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_BLOCKS_ONLY) && total_blocks && (!binfo || binfo_cap < total_blocks))
+		return fail(c, XZAMD_PROG_ERROR, "repair of bare Blocks: binfo must hold every Block (it is their table)", 0);
 	/* A batch must fit the device memory with room to spare: the work buffers take 100 - 165 bytes per input byte
 	 * (DESIGN.md section 2), and the runtime allocates kernel scratch (register spills of the parser) lazily at launch --
 	 * an allocation that fails there surfaces as an error of some later call, not as a clean out-of-memory here.  So
@@ -556,7 +591,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	 * is a few thousand latency-bound wavefronts, the structure build is HBM-bound, they share the GPU well.  The
 	 * single-phase kernels read the match structures while they code, so their batches stay serial. */
 	const int overlap_ok = two && !J->k.no_overlap;
-	J->defer = may_defer && overlap_ok && (flags & XZAMD_F_BLOCKS_ONLY) && total_blocks > 0;
+	J->defer = may_defer && overlap_ok && (flags & XZAMD_F_BLOCKS_ONLY) && total_blocks > 0 && !(flags & XZAMD_F_REPAIR);
 	/* a batch carried over from the previous call: it can only be finished underneath this call's front end when this call
 	 * runs the same two-stream scheme on the same streams; else it is finished first */
 	if (c->pend.active && !(overlap_ok && c->pend.J.st == st))
@@ -579,6 +614,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	J->segments = (flags & XZAMD_F_SEGMENTS) != 0;
 	J->resume = (flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && two;
 	J->verify = (flags & XZAMD_F_VERIFY) != 0;
+	J->repair = (flags & XZAMD_F_REPAIR) != 0;
 	/* the table of the encode before is that encode's: gone with this one (its memory too, unless this call fills it again) */
 	c->resume.valid = 0;
 	if (c->resume_tab.p && !J->resume && !c->pend.active) {
@@ -1536,7 +1572,17 @@ int xzamd_encode_device_(xzamd_ctx *c,
 		c->resume.stride = XZAMD_RESUME_BYTES(J.m.model_slots); c->resume.nrec = J.rec_done;
 		c->resume.nblocks = J.total_blocks; c->resume.block_size = J.block_size; c->resume.in_size = in_size;
 	}
-	if (rc == XZAMD_OK && J.verify) {
+	if (rc == XZAMD_OK && J.repair) {
+		/* verified and repaired encode: per-Block verdicts; the Blocks the device decoder rejects are re-encoded and spliced */
+		uint64_t ns = J.opos;
+		rc = xzamd_repair_encoded_(c, J.d_out, J.opos, J.out_cap, J.d_in, in_size, J.block_size, J.opt, J.check, J.whole, J.binfo,
+				J.binfo_cap, J.total_blocks, &ns, J.st);
+		if (rc == XZAMD_OK) {
+			*out_size = ns;
+			c->stats.out_bytes = ns;
+		}
+		c->stats.ms_verify = c->report.ms_verify;
+	} else if (rc == XZAMD_OK && J.verify) {
 		/* verified encode: the finished Stream against the input, before the caller sees XZAMD_OK (its message and report stay) */
 		rc = xzamd_verify_kept_(c, J.d_out, J.opos, J.d_in, in_size, J.st);
 		c->stats.ms_verify = c->report.ms_verify;

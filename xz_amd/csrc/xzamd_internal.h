@@ -49,6 +49,13 @@ typedef struct {
 	const uint8_t *d_rec;           /* optional: nrec records of rec_stride bytes (kernels_api.h) */
 	uint32_t rec_stride, nrec;
 	xzamd_verify_report *report;    /* optional: units, Blocks, records, the first defect */
+	/* COLLECT mode (the per-Block verification, xzamd_verify_table_): one XZAMD_VSTEP_* per Block, in and out.  A Block that
+	 * fails a step is marked with it and taken out of the later steps, the run goes on for the others, and the call returns
+	 * XZAMD_DATA_ERROR at the end when any Block is marked.  A Block marked on entry (its header was bad) is left out from the
+	 * start.  The report names what a run without `steps` would have stopped at. */
+	uint8_t *steps;                 /* optional: nb bytes */
+	int plain_history;              /* with d_expected: it is only compared with; the units are those of a decode without it (dictionary
+	                                 * resets, history = the output itself) */
 } xzamd_dec_job;
 
 /* The resume table a context keeps of its last encode with XZAMD_F_KEEP_RESUME / XZAMD_F_VERIFY (xzamd_host.c) */
@@ -69,6 +76,70 @@ int xzamd_debug_resume_poke_(xzamd_ctx *c, uint32_t record, int field, uint32_t 
 int xzamd_debug_resume_peek_(xzamd_ctx *c, uint32_t record, uint32_t hdr_out[8], uint32_t *nrec_out);
 int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j);
 const char *xzamd_block_step_msg_(uint32_t step);
+
+/* ---- per-Block verification and repair (xzamd_decode.c, xzamd_repair.c, xzamd_repair_plan.c; DESIGN.md 3.6 "Repair") ---- */
+/* Header, Footer and Index of the single Stream at d_xz -> one record per Block (malloc'ed, the caller frees) and the Check.
+ * A defect here is a defect of the whole Stream: the code of xzamd_stream_decode_device. */
+int xzamd_stream_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, xzamd_hdr_rec **recs, uint64_t *nb, int *check,
+		void *stream);
+/* The collecting verification of the Blocks `recs` name inside d_xz (a Stream, or bare Blocks): Block Headers (k_dec_headers),
+ * unit scan, decode, inverse filters, Checks and -- with d_original, whose byte recs[b].upos is the Block's first -- the
+ * per-Block comparison.  steps[b] = XZAMD_VSTEP_* of the first step Block b failed.  XZAMD_VT_KEPT: the units of the context's
+ * resume table when it fits.  XZAMD_VT_PRECISE: a Block that fails at "decode" or "check" with the original as history goes
+ * through once more with its own output as history, so that the step names a defect of the Stream and not one of the original
+ * (a Block-sequential decode; the repair, which re-encodes a bad Block whatever its step, does without).
+ * XZAMD_OK: every Block good; XZAMD_DATA_ERROR: some Block bad; else a failure of the call. */
+#define XZAMD_VT_KEPT 1
+#define XZAMD_VT_PRECISE 2
+int xzamd_verify_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, const xzamd_hdr_rec *recs, uint64_t nb, int check,
+		const uint8_t *d_original, uint64_t original_size, int mode, uint8_t *steps, xzamd_verify_report *report, void *stream);
+/* What an encode on the context would overwrite while a repair re-encodes Blocks on it: the kept resume table (taken out of
+ * the context, so that the re-encode neither frees nor replaces it) and the stats of the call being repaired */
+typedef struct {
+	void *tab; uint64_t tab_cap;
+	int valid; uint32_t stride, nrec; uint64_t nblocks, block_size, in_size;
+	xzamd_stats stats;
+} xzamd_ctx_saved;
+void xzamd_ctx_save_(xzamd_ctx *c, xzamd_ctx_saved *s);
+void xzamd_ctx_restore_(xzamd_ctx *c, const xzamd_ctx_saved *s);
+xzamd_repair_report *xzamd_ctx_repair_report_(xzamd_ctx *c);
+/* XZAMD_F_REPAIR on behalf of the batch encoder, which refers to it weakly (xzamd_repair.c): per-Block verification of the
+ * Stream (framed) or the bare Blocks (their table: binfo) just written to d_out, repair of the rejected ones.  binfo (optional
+ * when framed) is rewritten for the Blocks that moved. */
+int xzamd_repair_encoded_(xzamd_ctx *c, void *d_out, uint64_t size, uint64_t cap, const void *d_in, uint64_t in_size,
+		uint64_t block_size, const xzamd_lzma_options *opt, int check, int framed, xzamd_block_info *binfo, uint64_t binfo_cap,
+		uint64_t nblocks, uint64_t *new_size, void *stream);
+
+/* The splice layout of a repair: pure arithmetic, no device call (xzamd_repair_plan.c). */
+#define XZAMD_RP_KEEP 0u
+#define XZAMD_RP_CODED 1u       /* replaced by a re-encoded Block that lies whole in the scratch buffer */
+#define XZAMD_RP_STORED 2u      /* replaced by the stored form: uncompressed LZMA2 chunks of the original, filters dropped */
+#define XZAMD_RP_SEG_MAX (1ull << 20)   /* a kept run moves in pieces of this size (the gather runs one workgroup per segment) */
+typedef struct {
+	uint64_t pos;           /* in: of the Block Header in the old Stream */
+	uint64_t unpadded;      /* in: old Unpadded Size */
+	uint64_t usize;         /* in */
+	uint64_t uoff;          /* in: of the Block's first byte in the original */
+	uint32_t repl;          /* in: XZAMD_RP_* */
+	uint32_t pad_;
+	uint64_t src;           /* in: CODED: scratch offset of the re-encoded Block; STORED: scratch offset of the Block's Check bytes */
+	uint64_t new_unpadded;  /* CODED: in; KEEP, STORED: out */
+	uint64_t new_pos;       /* out */
+} xzamd_rp_block;
+/* segment kinds of the plan: 0 scratch, 1 lits, 2 the old Stream, 3 the original; dst = offset from tail_pos */
+typedef struct {
+	uint64_t first;         /* first replaced Block (nb: none, nothing else is filled in) */
+	uint64_t tail_pos;      /* the Stream is rewritten from here on: blocks[first].pos */
+	uint64_t tail_len;      /* new bytes from tail_pos to the end */
+	uint64_t new_size;      /* tail_pos + tail_len */
+	xzamd_copy_seg *segs; uint64_t nsegs;
+	uint8_t *lits; uint64_t lits_len;
+	uint64_t frame_off, frame_len;   /* framed: Index + Stream Footer inside lits */
+} xzamd_rp_plan;
+/* blocks: nb Blocks in Stream order, adjacent (pos[b + 1] = pos[b] + Unpadded Size rounded up to four).  framed: Index and
+ * Stream Footer follow the last Block.  Returns XZAMD_OK, XZAMD_MEM_ERROR or XZAMD_PROG_ERROR (a table that is not adjacent). */
+int xzamd_repair_plan_(xzamd_rp_block *blocks, uint64_t nb, int check, int framed, xzamd_rp_plan *plan);
+void xzamd_repair_plan_free_(xzamd_rp_plan *plan);
 
 double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt);   /* device work buffers per input byte of a batch */
 

@@ -138,6 +138,8 @@ struct lzma_internal_s {
 	int blk_open;                /* Block Header handed to the output queue, end of the Block not yet */
 	uint64_t blk_csize, blk_usize, blk_crc;       /* of the open Block: chunk chains so far, their input, its Check so far */
 	uint64_t segment_env;        /* XZAMD_SEGMENT_KIB << 10, 0 = lzma_mt_block_size of the chain */
+	int repair;                  /* XZAMD_REPAIR=1 (read at init; MT layout only): every job runs with XZAMD_F_REPAIR and is finished
+	                              * before the next one is launched */
 };
 
 static void *a_alloc(const lzma_allocator *a, size_t n)
@@ -344,8 +346,9 @@ static lzma_ret job_launch(lzma_internal *in, devslot *d, job *j, int io, int *r
 	void *cs = xzamd_ctx_stream_(d->ctx);
 	if (!injected && !(xzk_h2d(b->d_in, j->stage, n, cs) || xzk_sync(cs)) && (vlog("uploaded", j), 1))
 		*rc_out = xzamd_encode_device_(d->ctx, b->d_in, n, in->block_size, &j->opt, in->check,
-				in->single ? XZAMD_F_SEGMENTS : XZAMD_F_BLOCKS_ONLY, b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
-				&j->nblocks, NULL, (nd && *nd == '1') ? NULL : deferred);
+				in->single ? XZAMD_F_SEGMENTS : in->repair ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_REPAIR : XZAMD_F_BLOCKS_ONLY,
+				b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
+				&j->nblocks, NULL, ((nd && *nd == '1') || in->repair) ? NULL : deferred);
 	return LZMA_OK;
 }
 
@@ -677,6 +680,10 @@ static lzma_ret encoder_init(lzma_stream *strm, lzma_ret r, const xzamd_lzma_opt
 	in->timeout_ms = timeout;
 	in->single = single;
 	in->segment_env = segment_env;
+	{
+		const char *rp = getenv("XZAMD_REPAIR");
+		in->repair = !single && rp && *rp == '1';
+	}
 	in->sequence = ISEQ_RUN;
 	in->sseq = SEQ_HEADER;
 	in->fill = -1;

@@ -16,6 +16,12 @@
 
 static int g_devices = 1;
 
+/* hooks of the decoder harness (stub_xzk_dec.c), off unless it sets them: a trace line per call of the functions the
+ * device decoder's host code uses, and a real SHA-256 */
+void (*stub_xzk_trace)(const char *fmt, ...);
+int (*stub_xzk_sha256)(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint8_t *d_out32);
+#define TRACE(...) do { if (stub_xzk_trace) stub_xzk_trace(__VA_ARGS__); } while (0)
+
 int xzk_malloc(void **p, uint64_t bytes) { *p = malloc(bytes ? bytes : 1); return *p ? 0 : 2; }
 int xzk_free(void *p) { free(p); return 0; }
 int xzk_host_alloc(void **p, uint64_t bytes) { *p = malloc(bytes ? bytes : 1); return *p ? 0 : 2; }
@@ -172,19 +178,22 @@ int xzk_encode_syms(const xzamd_span_args *a, uint32_t nblocks, void *stream)
 
 int xzk_x86_bcj(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, void *stream)
 {
-	(void)d_in; (void)d_out; (void)n; (void)block_size; (void)nblocks; (void)stream;
+	(void)d_in; (void)d_out; (void)stream;
+	TRACE("x86_bcj(%u,%u,%u)", n, block_size, nblocks);
 	return 1;       /* filters are device work: not part of the host-logic tests */
 }
 int xzk_prefilter(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t kind, uint32_t dist,
 		void *stream)
 {
-	(void)d_in; (void)d_out; (void)n; (void)block_size; (void)nblocks; (void)kind; (void)dist; (void)stream;
+	(void)d_in; (void)d_out; (void)stream;
+	TRACE("prefilter(%u,%u,%u,%u,%u)", n, block_size, nblocks, kind, dist);
 	return 1;
 }
 int xzk_sha256_blocks(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint8_t *d_out32, void *stream)
 {
-	(void)d_in; (void)n; (void)block_size; (void)nblocks; (void)d_out32; (void)stream;
-	return 1;
+	(void)stream;
+	TRACE("sha256(%u,%u,%u)", n, block_size, nblocks);
+	return stub_xzk_sha256 ? stub_xzk_sha256(d_in, n, block_size, nblocks, d_out32) : 1;
 }
 
 static uint64_t t64[256];
@@ -205,10 +214,12 @@ static void crc_tables(void)
 int xzk_crc_blocks(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks,
 		uint32_t strip, int crc32, uint64_t *d_strip_crc, uint64_t *d_block_crc, void *stream)
 {
-	(void)strip; (void)d_strip_crc; (void)stream;
+	(void)d_strip_crc; (void)stream;
+	TRACE("crc(%u,%u,%u,%u,%d)", n, block_size, nblocks, strip, crc32);
 	pthread_once(&crc_once, crc_tables);
 	for (uint32_t b = 0; b < nblocks; ++b) {
 		const uint64_t bs = (uint64_t)b * block_size;
+		if (n == 0) d_block_crc[b] = 0;         /* (the decoder's Blocks of no bytes: the CRC of nothing) */
 		if (bs >= n) break;
 		const uint64_t be = n - bs < block_size ? n : bs + block_size;
 		if (crc32) {

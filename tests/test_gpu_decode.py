@@ -133,3 +133,56 @@ def test_block_checks_are_verified_or_refused(enc):
     xz, _ = enc.encode(t, preset=1, block_size=1 << 18)
     with pytest.raises(xz_amd.XzAmdError):
         enc.decode(xz.clone(), len(data) + 16, expected=t[: len(data) - 5].clone())
+
+
+def _golden_entry_codes():
+    """case name -> {entry: code} of the CPU characterisation of the decoder's host code (tests/test_host_decode.py): lines
+    "NAME | ENTRY code/blocks ... | ...", the entries `decode` and `file` being Encoder.decode and Encoder.decode_file"""
+    codes = {}
+    with open(os.path.join(os.path.dirname(FIX), "decode_host_trace.txt")) as fh:
+        for line in fh:
+            name, *entries = line.rstrip("\n").split(" | ")
+            if entries:
+                codes[name] = {e.split(" ")[0]: int(e.split(" ")[1].split("/")[0]) for e in entries}
+    return codes
+
+
+def test_single_stream_entry_answers_like_the_file_entry(enc):
+    """Encoder.decode reads Block framing through the same kernel (k_dec_headers) as Encoder.decode_file: the two answer
+    the same code for every reference fixture and for every single defect in the framing of Block 1 of a three-Block
+    Stream of 4 KiB Blocks.  Where the two entries differ by design -- files of several Streams, Stream Padding, which the
+    single-Stream entry does not read -- the recorded CPU trace names the file and both codes."""
+    import xz_amd
+    import test_gpu_decode_file as tf
+    if not o.have_ref():
+        pytest.skip("oracle/_ref not built")
+    golden = _golden_entry_codes()
+    files = sorted(glob.glob(os.path.join(os.path.dirname(FIX), "ref_files*", "*.xz")))
+    assert len(files) >= 43         # 28 + 7 + 8 files of the three fixture folders
+    ndiffer = 0
+    for p in files:
+        t = _cuda(open(p, "rb").read())
+        got = (tf._code(lambda: enc.decode(t, 1 << 20)), tf._code(lambda: enc.decode_file(t, 1 << 20)))
+        rec = golden[os.path.join(os.path.basename(os.path.dirname(p)), os.path.basename(p))]
+        if rec["decode"] != rec["file"]:
+            assert got == (rec["decode"], rec["file"]), p
+            ndiffer += 1
+        else:
+            assert got[0] == got[1], (p, got)
+    assert ndiffer == 6         # the six files of ref_files_concat with more than one Stream or with Stream Padding
+    data = o.corpus_mixed(2 * 4096 + 777, 41)
+    raw = o.ref_encode_mt(data, 1, block_size=4096)
+    _, blocks, _ = xz_amd.file_index(raw)
+    assert len(blocks) == 3
+    cases = tf._header_corruptions(raw, blocks)
+    assert len(cases) == 6
+    # (the recorded single-byte flips of a Block Header: no case where these two entries differ)
+    flips = [c for n, c in golden.items() if n.startswith("flip blockheader1 ")]
+    assert flips and all(c["decode"] == c["file"] for c in flips)
+    seen = set()
+    for name, bad in cases.items():
+        t = _cuda(bad)
+        got = (tf._code(lambda: enc.decode(t, len(data) + 16)), tf._code(lambda: enc.decode_file(t, len(data) + 16)))
+        assert got[0] == got[1] and got[0] in (8, 9), (name, got)
+        seen.add(got[0])
+    assert seen == {8, 9}

@@ -5,6 +5,9 @@ plan bookkeeping, layout), xzamd_frame.c (framing, stored Blocks) and xzamd_opti
 compiled with -fsanitize=address,undefined and, separately, -fsanitize=thread, on top of tests/host_stub/stub_xzk.c -- a CPU stand-in for the kernel layer whose "span kernel"
 emits LZMA2 uncompressed chunks -- and driven through the liblzma entry points by tests/host_stub/driver.c.  The
 Streams the host code frames must decode bit-exactly through the oracle decoder and the real reference decoder.
+The decoder's host code (xzamd_framing.c, xzamd_decode.c, xzamd_file.c) has a harness of its own on the same stand-in plus its
+decoder half (tests/host_stub/stub_xzk_dec.c, driver_decode.c): tests/test_host_decode.py, ASan/UBSan and a golden trace.
+The hooks that harness sets in stub_xzk.c are off here.
 Test infrastructure only: nothing here is linked into libxz_amd.so."""
 import os
 import shutil

@@ -1,5 +1,5 @@
-/* xzamd_block_parse.h -- the per-Block framing checks of the device .xz decoder, one text for the host (xzamd_decode.c,
- * xzamd_file.c) and for the device (k_dec_headers, lzma_decode.hip): Block Header, sizes against the Index, Block
+/* xzamd_block_parse.h -- the per-Block framing checks of the device .xz decoder, one text for the host (xzamd_framing.c)
+ * and for the device (k_dec_headers, lzma_decode.hip): Block Header, sizes against the Index, Block
  * Padding, the stored Check.  The checks and their order restate
  *   common/block_header_decoder.c:17-125    size byte, CRC32, reserved flags, the two optional VLIs, padding
  *   common/filter_flags_decoder.c:15-45,    Filter Flags: ids, sizes of properties, LZMA2 dictionary byte, delta distance,

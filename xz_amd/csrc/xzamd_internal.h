@@ -25,7 +25,7 @@ void xzamd_debug_decode_counters_(uint64_t out[3]);
 /* ... of the last decode launch of the process: units, Blocks, split mode of the scan (0 Block, 1 verification, 2 plain) */
 void xzamd_debug_decode_units_(uint64_t out[3]);
 
-/* The device part of a decode (xzamd_decode.c), shared by the single-Stream entry and the file entries (xzamd_file.c). */
+/* The device part of a decode (xzamd_decode.c), shared by the single-Stream entries and the file entries (xzamd_file.c). */
 typedef struct {
 	uint64_t first, count;          /* Blocks [first, first + count) of the job ... */
 	int check;                      /* ... carry this Check (the Blocks of one Stream) */
@@ -77,7 +77,7 @@ int xzamd_debug_resume_peek_(xzamd_ctx *c, uint32_t record, uint32_t hdr_out[8],
 int xzamd_dec_run_(xzamd_ctx *c, void *st, const xzamd_dec_job *j);
 const char *xzamd_block_step_msg_(uint32_t step);
 
-/* ---- per-Block verification and repair (xzamd_decode.c, xzamd_repair.c, xzamd_repair_plan.c; DESIGN.md 3.6 "Repair") ---- */
+/* ---- per-Block verification and repair (xzamd_framing.c, xzamd_decode.c, xzamd_repair.c, xzamd_repair_plan.c; DESIGN.md 3.6 "Repair") ---- */
 /* Header, Footer and Index of the single Stream at d_xz -> one record per Block (malloc'ed, the caller frees) and the Check.
  * A defect here is a defect of the whole Stream: the code of xzamd_stream_decode_device. */
 int xzamd_stream_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, xzamd_hdr_rec **recs, uint64_t *nb, int *check,
@@ -156,6 +156,44 @@ XZAMD_HIDDEN uint32_t xzamd_block_header_size_(uint64_t csize, uint64_t usize, c
 XZAMD_HIDDEN uint32_t xzamd_block_header_nosizes_(uint8_t out[12], uint8_t dict_byte);
 XZAMD_HIDDEN void xzamd_block_header_put_(uint8_t *out, uint32_t hs, uint64_t csize, uint64_t usize, uint8_t dict_byte,
 		const xzamd_lzma_options *opt);
+
+/* xzamd_framing.c: container bytes -> the tables a decoder run consumes */
+typedef struct {
+	const uint8_t *host;    /* the container in host memory, or */
+	const uint8_t *dev;     /* in device memory, read through st */
+	void *st;
+	uint64_t size;
+	uint64_t reads;         /* device-to-host reads so far */
+} xzamd_src;
+XZAMD_HIDDEN int xzamd_src_read_(xzamd_src *s, uint64_t off, void *buf, uint64_t n);
+/* Header, Footer and Index of the single Stream `s` -> one record per Block (malloc'ed, the caller frees) and the Check.
+ * An Index record with an Uncompressed Size above usize_max is a data error.  Returns 0 or the code; *msg. */
+XZAMD_HIDDEN int xzamd_stream_walk_(xzamd_src *s, uint64_t usize_max, xzamd_hdr_rec **recs, uint64_t *nb, int *check, const char **msg);
+/* The framing of every Stream of a file (walked from its end, Stream Padding included): Streams and Index records */
+typedef struct {
+	xzamd_xz_stream *streams;   /* file order */
+	uint64_t nstreams;
+	xzamd_hdr_rec *recs;        /* one per Block of the file, file order; upos = offset in the decoded file */
+	uint32_t *rec_stream;
+	uint64_t nrecs;
+	uint64_t usize;
+} xzamd_walk;
+XZAMD_HIDDEN int xzamd_file_walk_(xzamd_src *s, xzamd_walk *w, const char **msg);
+XZAMD_HIDDEN void xzamd_walk_free_(xzamd_walk *w);
+/* The Block table of n records: xzb_block per Block, on the host for a container in host memory, as k_dec_headers else.
+ * err[b] is the verdict on Block b (code 0: good); hb / hc / stored of a bad Block are not to be used.  Returns 0, or the
+ * code of a failure of the call itself (memory, device) with *msg. */
+typedef struct {
+	xzamd_dec_block *hb;
+	xzamd_dec_chain *hc;
+	uint8_t *stored;            /* XZAMD_HDR_CHECK_BYTES per Block */
+	xzamd_hdr_err *err;
+} xzamd_blocks;
+XZAMD_HIDDEN int xzamd_block_table_(xzamd_src *s, const xzamd_hdr_rec *recs, uint64_t n, xzamd_blocks *B, uint64_t *launches,
+		const char **msg);
+/* the code of the first bad Block of the table in file order (0: none) and the text of its defect */
+XZAMD_HIDDEN int xzamd_blocks_first_bad_(const xzamd_blocks *B, uint64_t n, const char **msg);
+XZAMD_HIDDEN void xzamd_blocks_free_(xzamd_blocks *B);
 
 /* xzamd_options.c: the encode mode of an option set */
 typedef struct {

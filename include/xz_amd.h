@@ -242,7 +242,7 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
  * (xzamd_stream_verify_blocks_device names every bad Block, xzamd_stream_repair_device replaces them; XZAMD_F_REPAIR does both).
  * (Known at this version: a Block whose first piece is stored raw -- e.g. 512 KiB of random bytes in front of text -- can come
  * out with its first LZMA chunk lacking the properties byte, which every decoder rejects; XZAMD_F_VERIFY is what reports it,
- * XZAMD_F_REPAIR delivers a valid Stream for it.)
+ * XZAMD_F_REPAIR delivers a valid Stream for it; the same holds for the segments of XZAMD_F_SINGLE.)
  * Either flag with XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS is XZAMD_OPTIONS_ERROR: there is no container to read.
  * XZAMD_F_REPAIR (implies XZAMD_F_VERIFY): VERIFIED AND REPAIRED ENCODE.  The verification is the per-Block one
  * (xzamd_stream_verify_blocks_device); every Block it rejects is re-encoded from its slice of d_in and spliced into d_out as
@@ -251,11 +251,25 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
  * final, passing verification.  A Stream without a bad Block is byte for byte that of a call without the flag.
  * XZAMD_F_REPAIR | XZAMD_F_BLOCKS_ONLY is allowed (binfo must then hold every Block: the Block table is read from it and from
  * the Block Headers in d_out; the splice rewrites the bare Blocks and binfo).  XZAMD_F_REPAIR | XZAMD_F_SEGMENTS is
- * XZAMD_OPTIONS_ERROR: the chunk chains of the single-Block Stream of lzma_stream_encoder are not Blocks; repairing them is out
- * of scope at this version.  A call with XZAMD_F_REPAIR never defers its back end. */
+ * XZAMD_OPTIONS_ERROR: the chunk chains of a single-Block Stream are not Blocks -- they are verified and replaced through
+ * XZAMD_F_SINGLE below, or on their own with xzamd_chains_verify_device / xzamd_chains_repair_device.  A call with
+ * XZAMD_F_REPAIR never defers its back end.
+ * XZAMD_F_SINGLE: the call writes the complete SINGLE-BLOCK Stream lzma_stream_encoder / lzma_easy_encoder of this library write
+ * (DESIGN.md 3.7), on the device: Stream Header, the 12-byte Block Header without sizes, the chunk chains of the segments of
+ * block_size bytes (exactly what XZAMD_F_SEGMENTS writes), 0x00 and Block Padding, the Check folded from the segments' CRCs, an
+ * Index of one record, Stream Footer.  binfo describes the SEGMENTS as under XZAMD_F_SEGMENTS, with offsets inside the Stream;
+ * *nblocks = their number.  An empty input gives a Stream without a Block.  XZAMD_F_SINGLE | XZAMD_F_KEEP_RESUME, | XZAMD_F_VERIFY
+ * and | XZAMD_F_REPAIR are valid and act on the chains BEFORE they are framed (the resume records name segments): with
+ * XZAMD_F_VERIFY a defect is XZAMD_DATA_ERROR, *out_size is still set to the framed Stream and the report's first_bad_block is
+ * the segment; with XZAMD_F_REPAIR the rejected segments are replaced (xzamd_chains_repair_device), the delivered Stream is
+ * valid and xzamd_get_repair_report counts segments.  With XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS, with SHA-256 or with a filter
+ * in front of LZMA2: XZAMD_OPTIONS_ERROR.  Not covered: xzamd_stream_verify_device on the framed Stream cuts no units at the
+ * kept records of a Stream of several segments (they name segments, the Stream has one Block): it verifies with one unit per
+ * segment, at the dictionary resets. */
 #define XZAMD_F_KEEP_RESUME 4u
 #define XZAMD_F_VERIFY 8u
 #define XZAMD_F_REPAIR 16u
+#define XZAMD_F_SINGLE 32u
 
 typedef struct {
 	uint64_t unpadded_size;      /* Index record field 1 (block_util.c:45-76) */
@@ -362,6 +376,30 @@ int xzamd_stream_repair_device(xzamd_ctx *ctx, void *d_xz, uint64_t xz_size, uin
 		uint64_t *new_size, xzamd_repair_report *report, void *stream);
 /* The report of the context's last repair (xzamd_stream_repair_device or an encode with XZAMD_F_REPAIR). */
 void xzamd_get_repair_report(const xzamd_ctx *ctx, xzamd_repair_report *out);
+
+/* BARE CHUNK CHAINS: the segments of an XZAMD_F_SEGMENTS encode (the payload of the single-Block Stream of lzma_stream_encoder),
+ * verified and repaired as the Blocks of a Stream are.  binfo[i] is what XZAMD_F_SEGMENTS fills in: out_offset and total_size =
+ * where chain i lies in d_chains (`size` bytes) and how long it is, uncompressed_size, unpadded_size = the segment's Check value
+ * (none: 0, CRC32 zero-extended, CRC64); segment i covers the original from the sum of the sizes in front of it.  opt gives the
+ * dictionary size (and, for the repair, what to re-encode with).  Checks none / CRC32 / CRC64.
+ * xzamd_chains_verify_device: one XZAMD_VSTEP_* per segment in seg_steps.  A chain is exactly total_size bytes, starts with a
+ * dictionary reset and holds no 0x00 end marker ("grammar" otherwise); it decodes as a unit of its own, with d_original also cut
+ * at its state resets or -- when the context keeps the resume table of the encode that made the chains -- at the records, which
+ * name segments; the decoded bytes are checked against the row's CRC ("check") and the original ("compare").  d_original may be
+ * NULL.  Codes as xzamd_stream_verify_blocks_device: XZAMD_OK, XZAMD_DATA_ERROR (some segment bad), XZAMD_BUF_ERROR (steps_cap <
+ * nsegments).
+ * xzamd_chains_repair_device: the chains must lie back to back and end at `size`.  Every rejected segment is re-encoded from its
+ * slice of the original -- rung 1: opt single-phase, 256 KiB spans (the fast parser for an option set that cannot run that way);
+ * rung 2: the stored chain, 0x01 + 64 KiB, then 0x02 chunks -- and spliced in: every chain behind the first replaced one moves,
+ * binfo[i].out_offset / total_size are rewritten, the CRC and the uncompressed size stay.  The spliced chains pass the verdicts
+ * once more before the call returns.  All or nothing: on any error chains and binfo are what they were.  XZAMD_BUF_ERROR: the
+ * repaired chains need *new_size > cap bytes.  Codes and report as xzamd_stream_repair_device (its counts are segments). */
+int xzamd_chains_verify_device(xzamd_ctx *ctx, const void *d_chains, uint64_t size, const xzamd_block_info *binfo, uint64_t nsegments,
+		const xzamd_lzma_options *opt, int check, const void *d_original, uint64_t original_size, uint8_t *seg_steps,
+		uint64_t steps_cap, xzamd_verify_report *report, void *stream);
+int xzamd_chains_repair_device(xzamd_ctx *ctx, void *d_chains, uint64_t size, uint64_t cap, xzamd_block_info *binfo, uint64_t nsegments,
+		const xzamd_lzma_options *opt, int check, const void *d_original, uint64_t original_size, uint64_t *new_size,
+		xzamd_repair_report *report, void *stream);
 
 /* ---- whole .xz files: concatenated Streams, Stream Padding, file index, range decode ----
  * An .xz file is one or more Streams, each followed by Stream Padding (zero bytes, a multiple of four): what `xz -d`

@@ -8,6 +8,10 @@ verify only).
 usage: tools/bench_repair.py ask    [MiB=1024] [preset=6] [reps=3] [block MiB=24]   plain / verify / repair, alternating
        tools/bench_repair.py reject [MiB=1024] [preset=6] [reps=3] [block MiB=24]   1 and 4 Blocks rejected
        tools/bench_repair.py all    [MiB=1024] [preset=6] [reps=3] [block MiB=24]
+       tools/bench_repair.py single [MiB=1024] [preset=6] [reps=3]    the single-Block path: lzma_easy_encoder through one
+                                                                      lzma_code(LZMA_FINISH), host to host, default segments
+                                                                      (XZAMD_SEGMENT_KIB), without and -- where the library
+                                                                      honours it there -- with XZAMD_REPAIR=1, alternating
 Prints one line per figure: median, the runs, MB/s of the uncompressed size."""
 import os
 import sys
@@ -19,9 +23,45 @@ import xz_amd  # noqa: E402
 from bench_verify import line, timed  # noqa: E402
 
 
+def single(mib, preset, reps):
+    """XZAMD_REPAIR is read by lzma_easy_encoder at init: one process can time both settings side by side"""
+    import numpy as np
+    from bench_single_block import easy_encode
+    L = xz_amd.lib()
+    data = xz_amd.corpus_text(mib << 20, seed=1000)
+    out = np.empty(data.size // 2 + (1 << 20), dtype=np.uint8)
+    has = hasattr(L, "xzamd_chains_repair_device")
+    print(f"lib {'XZ_AMD_LIB' if os.environ.get('XZ_AMD_LIB') else 'in-tree'} ({os.path.basename(xz_amd.LIB_PATH)}); {mib} MiB corpus_text, "
+          f"preset {preset}, lzma_easy_encoder, XZAMD_SEGMENT_KIB={os.environ.get('XZAMD_SEGMENT_KIB', '-')}; repair of segments "
+          f"{'present' if has else 'absent'}", flush=True)
+    os.environ.pop("XZAMD_REPAIR", None)
+    os.environ.pop("XZAMD_TEST_REPAIR_REJECT", None)
+    easy_encode(L, data, preset, out)                               # warm-up: buffers allocated and parked
+    kinds = [("XZAMD_REPAIR unset", None)] + ([("XZAMD_REPAIR=1", "1")] if has else [])
+    runs = {k: [] for k, _ in kinds}
+    sizes = {}
+    for _ in range(reps):
+        for k, v in kinds:
+            if v is None:
+                os.environ.pop("XZAMD_REPAIR", None)
+            else:
+                os.environ["XZAMD_REPAIR"] = v
+            dt, sizes[k] = easy_encode(L, data, preset, out)
+            runs[k].append(dt)
+    os.environ.pop("XZAMD_REPAIR", None)
+    m0 = line(f"(s) lzma_easy_encoder, {kinds[0][0]}", runs[kinds[0][0]], data.size, f"; {sizes[kinds[0][0]]} bytes")
+    for k, _ in kinds[1:]:
+        m = line(f"(s) lzma_easy_encoder, {k}", runs[k], data.size, f"; {sizes[k]} bytes")
+        print(f"(s) cost of {k}: {(m - m0) * 1e3:+.1f} ms = {(m / m0 - 1) * 100:+.2f} %", flush=True)
+    xz_amd.lib().xzamd_release_parked()
+
+
 def main():
     import torch
     cmd = sys.argv[1] if len(sys.argv) > 1 else ""
+    if cmd == "single":
+        a = sys.argv[2:]
+        return single(int(a[0]) if a else 1024, int(a[1]) if len(a) > 1 else 6, int(a[2]) if len(a) > 2 else 3)
     if cmd not in ("ask", "reject", "all"):
         sys.exit(__doc__)
     a = sys.argv[2:]

@@ -22,6 +22,7 @@ F_SEGMENTS = 2
 F_KEEP_RESUME = 4
 F_VERIFY = 8
 F_REPAIR = 16
+F_SINGLE = 32
 VSTEPS = ("none", "grammar", "decode", "check", "compare")     # XZAMD_VSTEP_*
 NO_BLOCK = 0xFFFFFFFFFFFFFFFF
 BCJ_X86 = 4
@@ -164,6 +165,13 @@ def lib():
                                                      C.POINTER(RepairReport), C.c_void_p]
             l.xzamd_get_repair_report.restype = None
             l.xzamd_get_repair_report.argtypes = [C.c_void_p, C.POINTER(RepairReport)]
+        if hasattr(l, "xzamd_chains_repair_device"):    # (an older library lacks the bare chunk chains)
+            l.xzamd_chains_verify_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BlockInfo), C.c_uint64,
+                                                     C.POINTER(LzmaOptions), C.c_int, C.c_void_p, C.c_uint64,
+                                                     C.c_void_p, C.c_uint64, C.POINTER(VerifyReport), C.c_void_p]
+            l.xzamd_chains_repair_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(BlockInfo),
+                                                     C.c_uint64, C.POINTER(LzmaOptions), C.c_int, C.c_void_p, C.c_uint64,
+                                                     C.POINTER(C.c_uint64), C.POINTER(RepairReport), C.c_void_p]
         l.xzamd_debug_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         l.xzamd_trace_enable.argtypes = [C.c_void_p, C.c_uint32]
         l.xzamd_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -304,7 +312,8 @@ class Encoder:
         return s
 
     def encode(self, data, opts=None, preset=6, block_size=0, check=CHECK_CRC64,
-               span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0, repair=False):
+               span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0, repair=False,
+               single=False):
         """Encode a CUDA uint8 tensor into an .xz Stream (CUDA uint8 tensor).
 
         Returns (out_tensor_view, block_infos). Runs on torch's current stream.
@@ -316,6 +325,10 @@ class Encoder:
         repair: verified and repaired encode (XZAMD_F_REPAIR) -- every Block the device decoder rejects is re-encoded and
         spliced in before the call returns; `repair_report()` says what happened, the block infos are those of the
         repaired Stream.  Allowed with blocks_only.
+        single: the single-Block Stream of lzma_stream_encoder (XZAMD_F_SINGLE), coded in segments of `block_size` bytes;
+        the block infos describe the segments (offset and length of each chunk chain inside the Stream, its CRC in
+        unpadded_size).  Combinable with verify, keep_resume and repair, which then act on the segments' chains;
+        Checks none / CRC32 / CRC64, no filter in front of LZMA2.
 
         Every XzAmdError raised here carries `code` (the XZAMD_* value; it used to be None for encode failures) and
         `stream` (what was written: empty unless the failure is a verification defect).
@@ -345,7 +358,7 @@ class Encoder:
         rc = lib().xzamd_stream_encode_device(
             self._ctx, C.c_void_p(data.data_ptr()), n, bs, C.byref(opts), check,
             (F_BLOCKS_ONLY if blocks_only else 0) | (F_VERIFY if verify else 0) | (F_KEEP_RESUME if keep_resume else 0)
-            | (F_REPAIR if repair else 0) | flags,
+            | (F_REPAIR if repair else 0) | (F_SINGLE if single else 0) | flags,
             C.c_void_p(out.data_ptr()), out.numel(),
             C.byref(out_size), binfo, max(nblocks, 1), C.byref(nb), C.c_void_p(stream))
         if rc != 0:
@@ -403,6 +416,53 @@ class Encoder:
         if rc == 9 and not any(steps[: nb.value]):
             raise XzAmdError("xzamd_stream_verify_blocks_device failed (9)" + self._detail(), rc)
         return [VSTEPS[v] if v < len(VSTEPS) else str(v) for v in steps[: nb.value]]
+
+    def _chain_args(self, chains, block_infos, original, opts, preset):
+        import torch
+        for t in (chains,) + ((original,) if original is not None else ()):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == chains.device
+        if opts is None:
+            opts = preset_options(preset)
+        n = len(block_infos)
+        binfo = (BlockInfo * max(n, 1))()
+        for i, b in enumerate(block_infos):
+            binfo[i].unpadded_size, binfo[i].uncompressed_size = b.unpadded_size, b.uncompressed_size
+            binfo[i].out_offset, binfo[i].total_size = b.out_offset, b.total_size
+        torch.cuda.current_stream(chains.device).synchronize()
+        return opts, n, binfo
+
+    def verify_chains(self, chains, block_infos, original=None, opts=None, preset=6, check=CHECK_CRC64):
+        """Per-segment verification of bare chunk chains: `chains` (CUDA uint8 tensor) and `block_infos` as
+        encode(flags=F_SEGMENTS) returns them -- out_offset / total_size name a chain inside `chains`, unpadded_size is the
+        segment's CRC.  Against `original` when given.  One step name of VSTEPS per segment, "none" = good; bad segments do
+        not raise.  `verify_report()` has the details."""
+        opts, n, binfo = self._chain_args(chains, block_infos, original, opts, preset)
+        steps = (C.c_uint8 * max(n, 1))()
+        rc = lib().xzamd_chains_verify_device(self._ctx, C.c_void_p(chains.data_ptr()), chains.numel(), binfo, n,
+                                              C.byref(opts), check,
+                                              C.c_void_p(original.data_ptr()) if original is not None else None,
+                                              original.numel() if original is not None else 0, steps, n, None, None)
+        if rc not in (0, 9) or (rc == 9 and not any(steps[:n])):
+            raise XzAmdError(f"xzamd_chains_verify_device failed ({rc})" + self._detail(), rc)
+        return [VSTEPS[v] if v < len(VSTEPS) else str(v) for v in steps[:n]]
+
+    def repair_chains(self, buf, size, block_infos, original, opts=None, preset=6, check=CHECK_CRC64):
+        """Repair, in place, the chunk chains in the first `size` bytes of the CUDA uint8 tensor `buf` (its capacity: the
+        whole tensor): the segments the device decoder rejects are re-encoded from `original` and spliced in, the chains
+        behind them move.  All or nothing: an XzAmdError (code 10 when `buf` is too small, with `.new_size`) leaves chains
+        and block infos as they were (`.block_infos`: what the library left in its table).  Returns (view of the repaired chains, the rewritten block infos, report dict)."""
+        assert 0 <= size <= buf.numel()
+        opts, n, binfo = self._chain_args(buf, block_infos, original, opts, preset)
+        ns = C.c_uint64(0)
+        rc = lib().xzamd_chains_repair_device(self._ctx, C.c_void_p(buf.data_ptr()), size, buf.numel(), binfo, n,
+                                              C.byref(opts), check, C.c_void_p(original.data_ptr()), original.numel(),
+                                              C.byref(ns), None, None)
+        if rc != 0:
+            err = XzAmdError(f"xzamd_chains_repair_device failed ({rc})" + self._detail(), rc)
+            err.new_size = ns.value
+            err.block_infos = list(binfo)[:n]
+            raise err
+        return buf[: ns.value], list(binfo)[:n], self.repair_report()
 
     def repair_report(self):
         """The report of this context's last repair (`repair`, or an encode with repair=True) as a dict named like the

@@ -268,6 +268,12 @@ typedef struct {
  * whose records are all void (stored, or repaired) has the units of split 1 */
 int xzk_dec_scan(const uint8_t *d_xz, xzamd_dec_block *d_blocks, uint32_t nblocks, xzamd_dec_unit *d_units,
 		uint32_t units_cap, int split, const uint8_t *d_rec, uint32_t rec_stride, uint32_t nrec, void *stream);
+/* The same scan over BARE chunk chains (the segments of an XZAMD_F_SEGMENTS encode): row i of d_blocks names chain i -- cpos = its
+ * first byte in d_chains, csize = its length, exactly; usize; dict_size.  A chain has no 0x00 end marker: it ends at c == csize
+ * with u == usize, a 0x00 control byte inside it is error 6, and it must start with a dictionary reset.  The split modes are those
+ * of xzk_dec_scan; the `block` of a unit and of a resume record is the chain's index. */
+int xzk_dec_scan_chains(const uint8_t *d_chains, xzamd_dec_block *d_blocks, uint32_t nchains, xzamd_dec_unit *d_units,
+		uint32_t units_cap, int split, const uint8_t *d_rec, uint32_t rec_stride, uint32_t nrec, void *stream);
 /* d_expected: one wavefront per unit, history read from it.  Else per_unit != 0: one wavefront per unit (units that start
  * at dictionary resets, split 2), history = d_out; per_unit == 0: one wavefront per Block. */
 /* d_rec (split 3 only, else NULL): a unit with a record starts from it instead of from a state reset. */

@@ -43,6 +43,12 @@ __device__ __forceinline__ const uint32_t* rec_hdr(const uint8_t* tab, uint32_t 
 }
 
 // One thread per Block: walk the LZMA2 chunk chain, validate the grammar, list the units.
+// CHAINS: the table names BARE chunk chains (the segments of a single-Block Stream, XZAMD_F_SEGMENTS) instead of the LZMA2 data
+// of Blocks: a chain is exactly csize bytes, has no 0x00 end marker (the byte behind it is the first control byte of the next
+// chain, or lies outside the buffer) and ends at c == csize with u == usize; a 0x00 inside it is DEC_SIZE_MISMATCH.  It must
+// start with a dictionary reset like any Block's data, so it is a unit of its own on the same grounds.  A template parameter:
+// the Block instance compiles to what it compiled to without it.
+template <bool CHAINS>
 __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz, xzamd_dec_block* __restrict__ blocks,
         uint32_t nblocks, xzamd_dec_unit* __restrict__ units, uint32_t units_cap, int split,
         const uint8_t* __restrict__ rec_tab, uint32_t rec_stride, uint32_t nrec)
@@ -72,7 +78,10 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
     }
     while (c < B.csize) {
         const uint32_t ctl = p[c];
-        if (ctl == 0x00) { ++c; ended = true; break; }
+        if (ctl == 0x00) {
+            if (CHAINS) { err = DEC_SIZE_MISMATCH; break; }
+            ++c; ended = true; break;
+        }
         bool starts_unit = nunits == 0;
         uint64_t hs, cs, us;
         if (ctl >= 0x80) {
@@ -127,7 +136,7 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
         c += hs + cs;
         u += us;
     }
-    if (err == DEC_OK && (!ended || c != B.csize || u != B.usize)) err = DEC_SIZE_MISMATCH;
+    if (err == DEC_OK && ((!CHAINS && !ended) || c != B.csize || u != B.usize)) err = DEC_SIZE_MISMATCH;
     if (err == DEC_OK && split == 3) {
         // a record left over: its span start lies behind the Block's last chunk
         while (r < nrec && rec_hdr(rec_tab, rec_stride, r)[0] == b && (rec_hdr(rec_tab, rec_stride, r)[2] >> 24) == XZAMD_RK_VOID) ++r;
@@ -1026,7 +1035,17 @@ int xzk_dec_scan(const uint8_t* d_xz, xzamd_dec_block* d_blocks, uint32_t nblock
 {
     if (nblocks == 0) return 0;
     if (split == 3 && (!d_rec || rec_stride < XZAMD_RESUME_HDR || (rec_stride & 15u))) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_dec_scan, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_xz, d_blocks, nblocks,
+    hipLaunchKernelGGL(k_dec_scan<false>, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_xz, d_blocks, nblocks,
+            d_units, units_cap, split, d_rec, rec_stride, split == 3 ? nrec : 0u);
+    return (int)hipGetLastError();
+}
+
+int xzk_dec_scan_chains(const uint8_t* d_chains, xzamd_dec_block* d_blocks, uint32_t nchains, xzamd_dec_unit* d_units,
+        uint32_t units_cap, int split, const uint8_t* d_rec, uint32_t rec_stride, uint32_t nrec, void* stream_)
+{
+    if (nchains == 0) return 0;
+    if (split == 3 && (!d_rec || rec_stride < XZAMD_RESUME_HDR || (rec_stride & 15u))) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dec_scan<true>, dim3((nchains + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_chains, d_blocks, nchains,
             d_units, units_cap, split, d_rec, rec_stride, split == 3 ? nrec : 0u);
     return (int)hipGetLastError();
 }

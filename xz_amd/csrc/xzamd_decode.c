@@ -216,6 +216,10 @@ static int run_history_(dec_run *r)
 /* scan: the units of every Block (k_dec_scan) -> unit_first, total_units, the report, dec_last_units.  A Block with more state
  * resets than the table anticipates sends every Block through a second pass, one unit per Block (compared afterwards all the
  * same; in collect mode the Blocks the first pass marked stay marked -- their defect does not depend on the split). */
+/* (the scan of bare chains is referred to weakly: a build of this unit over a kernel layer without it has no chain jobs) */
+extern int xzk_dec_scan_chains(const uint8_t *d_chains, xzamd_dec_block *d_blocks, uint32_t nchains, xzamd_dec_unit *d_units,
+		uint32_t units_cap, int split, const uint8_t *d_rec, uint32_t rec_stride, uint32_t nrec, void *stream) __attribute__((weak));
+
 static int run_scan_(dec_run *r)
 {
 	const xzamd_dec_job *j = r->j;
@@ -223,14 +227,16 @@ static int run_scan_(dec_run *r)
 	xzamd_dec_block *hb = j->hb;
 	uint64_t recs_used = 0;
 	int rc;
+	if (j->chains && !xzk_dec_scan_chains) RUN_FAIL(r, XZAMD_OPTIONS_ERROR, "this build has no scan of bare chunk chains");
 	RUN_DEV(r, xzk_malloc(&r->d_blocks, nb * sizeof(xzamd_dec_block)) || xzk_malloc(&r->d_misc, 4096 + 4 * nb)
 			|| xzk_malloc(&r->d_first, 4 * (nb + 1)), "hipMalloc");
 	for (int pass = 0; ; ++pass) {
 		int overflow = 0;
 		RUN_DEV(r, xzk_malloc(&r->d_units, (uint64_t)r->units_cap * nb * sizeof(xzamd_dec_unit)), "hipMalloc");
 		RUN_DEV(r, xzk_h2d(r->d_blocks, hb, nb * sizeof(xzamd_dec_block), r->st), "h2d blocks");
-		RUN_DEV(r, xzk_dec_scan(j->d_xz, (xzamd_dec_block *)r->d_blocks, r->nbk, (xzamd_dec_unit *)r->d_units, r->units_cap, r->split,
-				r->split == 3 ? j->d_rec : NULL, j->rec_stride, j->nrec, r->st), "scan launch");
+		RUN_DEV(r, (j->chains ? xzk_dec_scan_chains : xzk_dec_scan)(j->d_xz, (xzamd_dec_block *)r->d_blocks, r->nbk,
+				(xzamd_dec_unit *)r->d_units, r->units_cap, r->split, r->split == 3 ? j->d_rec : NULL, j->rec_stride, j->nrec, r->st),
+				"scan launch");
 		launches_(j, 1);
 		RUN_DEV(r, xzk_d2h(hb, r->d_blocks, nb * sizeof(xzamd_dec_block), r->st) || xzk_sync(r->st), "d2h blocks");
 		reads_(j, 1);
@@ -662,6 +668,20 @@ done:
 	return rc;
 }
 
+int xzamd_verify_job_(xzamd_ctx *c, void *st, xzamd_dec_job *job, uint64_t utotal, int mode, xzamd_verify_report *rp)
+{
+	int rc;
+	if (mode & XZAMD_VT_KEPT) {
+		xzamd_resume_view tab;
+		xzamd_ctx_resume_(c, &tab);
+		job_take_table_(job, &tab, utotal);
+	}
+	rc = xzamd_dec_run_(c, st, job);
+	if (rc == XZAMD_DATA_ERROR && job->d_expected && (mode & XZAMD_VT_PRECISE))
+		rc = verify_again_(c, st, job, job->steps, rp);
+	return rc;
+}
+
 int xzamd_verify_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, const xzamd_hdr_rec *recs, uint64_t nb, int check,
 		const uint8_t *d_original, uint64_t original_size, int mode, uint8_t *steps, xzamd_verify_report *rp, void *st)
 {
@@ -705,14 +725,7 @@ int xzamd_verify_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, con
 	job.allow_split = ((uintptr_t)d_original & 15) == 0;
 	job.report = rp;
 	job.steps = steps;
-	if (mode & XZAMD_VT_KEPT) {
-		xzamd_resume_view tab;
-		xzamd_ctx_resume_(c, &tab);
-		job_take_table_(&job, &tab, utotal);
-	}
-	rc = xzamd_dec_run_(c, st, &job);
-	if (rc == XZAMD_DATA_ERROR && d_original && (mode & XZAMD_VT_PRECISE))
-		rc = verify_again_(c, st, &job, steps, rp);
+	rc = xzamd_verify_job_(c, st, &job, utotal, mode, rp);
 done:
 	xzk_sync(st);
 	if (d_tmp) xzk_free(d_tmp);

@@ -355,6 +355,14 @@ extern int xzamd_verify_kept_(xzamd_ctx *c, const void *d_xz, uint64_t xz_size, 
 extern int xzamd_repair_encoded_(xzamd_ctx *c, void *d_out, uint64_t size, uint64_t cap, const void *d_in, uint64_t in_size,
 		uint64_t block_size, const xzamd_lzma_options *opt, int check, int framed, xzamd_block_info *binfo, uint64_t binfo_cap,
 		uint64_t nblocks, uint64_t *new_size, void *stream) __attribute__((weak));
+/* ... and the unit of the bare chunk chains (xzamd_chains.c): without it there is no XZAMD_F_SINGLE, and XZAMD_F_SEGMENTS takes
+ * none of the three flags */
+extern int xzamd_chains_encoded_(xzamd_ctx *c, void *d_out, uint64_t size, uint64_t cap, const void *d_in, uint64_t in_size,
+		const xzamd_lzma_options *opt, int check, int repair, xzamd_block_info *binfo, uint64_t nseg, uint64_t *new_size,
+		void *stream) __attribute__((weak));
+extern int xzamd_single_encode_(xzamd_ctx *c, const void *d_in, uint64_t in_size, uint64_t block_size, const xzamd_lzma_options *opt,
+		int check, uint32_t flags, void *d_out, uint64_t out_cap, uint64_t *out_size, xzamd_block_info *binfo, uint64_t binfo_cap,
+		uint64_t *nsegments, void *stream) __attribute__((weak));
 xzamd_repair_report *xzamd_ctx_repair_report_(xzamd_ctx *c) { return &c->repair; }
 /* A repair re-encodes Blocks on the context of the call it repairs: the kept table leaves the context meanwhile (the
  * re-encode would free it), the stats of the repaired call come back afterwards */
@@ -502,9 +510,13 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		flags |= XZAMD_F_BLOCKS_ONLY;
 	if ((unsigned)check > 15)
 		return fail(c, XZAMD_PROG_ERROR, "check id out of range", 0);
-	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_SEGMENTS))
+	/* (internal callers only: the three flags act on the chains of the segments, xzamd_chains.c) */
+	const int chains = (flags & XZAMD_F_CHAINS_) != 0;
+	if (chains && (!(flags & XZAMD_F_SEGMENTS) || !xzamd_chains_encoded_))
+		return fail(c, XZAMD_OPTIONS_ERROR, "chains: this build has no unit for bare chunk chains", 0);
+	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_SEGMENTS) && !chains)
 		return fail(c, XZAMD_OPTIONS_ERROR, "repair: Blocks only, not the chunk chains of XZAMD_F_SEGMENTS", 0);
-	if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && (flags & XZAMD_F_BLOCKS_ONLY) && !(flags & XZAMD_F_REPAIR))
+	if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && (flags & XZAMD_F_BLOCKS_ONLY) && !(flags & XZAMD_F_REPAIR) && !chains)
 		return fail(c, XZAMD_OPTIONS_ERROR, "keep_resume / verify need a whole Stream: not with XZAMD_F_BLOCKS_ONLY or XZAMD_F_SEGMENTS", 0);
 	if (flags & XZAMD_F_REPAIR) {
 		if (!xzamd_repair_encoded_)
@@ -553,7 +565,8 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		return fail(c, XZAMD_OPTIONS_ERROR, "block_size too large for one device batch", 0);
 
 	const uint64_t total_blocks = (in_size + block_size - 1) / block_size;
-	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_BLOCKS_ONLY) && total_blocks && (!binfo || binfo_cap < total_blocks))
+	if ((flags & (XZAMD_F_REPAIR | (chains ? XZAMD_F_VERIFY : 0u))) && (flags & XZAMD_F_BLOCKS_ONLY) && total_blocks
+			&& (!binfo || binfo_cap < total_blocks))
 		return fail(c, XZAMD_PROG_ERROR, "repair of bare Blocks: binfo must hold every Block (it is their table)", 0);
 	/* A batch must fit the device memory with room to spare: the work buffers take 100 - 165 bytes per input byte
 	 * (DESIGN.md section 2), and the runtime allocates kernel scratch (register spills of the parser) lazily at launch --
@@ -591,7 +604,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	 * is a few thousand latency-bound wavefronts, the structure build is HBM-bound, they share the GPU well.  The
 	 * single-phase kernels read the match structures while they code, so their batches stay serial. */
 	const int overlap_ok = two && !J->k.no_overlap;
-	J->defer = may_defer && overlap_ok && (flags & XZAMD_F_BLOCKS_ONLY) && total_blocks > 0 && !(flags & XZAMD_F_REPAIR);
+	J->defer = may_defer && overlap_ok && (flags & XZAMD_F_BLOCKS_ONLY) && total_blocks > 0 && !(flags & (XZAMD_F_REPAIR | XZAMD_F_VERIFY));
 	/* a batch carried over from the previous call: it can only be finished underneath this call's front end when this call
 	 * runs the same two-stream scheme on the same streams; else it is finished first */
 	if (c->pend.active && !(overlap_ok && c->pend.J.st == st))
@@ -1468,6 +1481,14 @@ int xzamd_stream_encode_device(xzamd_ctx *c,
 		xzamd_block_info *binfo, uint64_t binfo_cap, uint64_t *nblocks_out,
 		void *stream)
 {
+	if (c && (flags & XZAMD_F_CHAINS_))
+		return fail(c, XZAMD_OPTIONS_ERROR, "unknown flag", 0);
+	if (c && (flags & XZAMD_F_SINGLE)) {
+		if (!xzamd_single_encode_)
+			return fail(c, XZAMD_OPTIONS_ERROR, "single: this build has no unit for bare chunk chains", 0);
+		return xzamd_single_encode_(c, d_in_, in_size, block_size, opt, check, flags & ~XZAMD_F_SINGLE, d_out_, out_cap, out_size, binfo,
+				binfo_cap, nblocks_out, stream);
+	}
 	return xzamd_encode_device_(c, d_in_, in_size, block_size, opt, check, flags, d_out_, out_cap, out_size, binfo, binfo_cap,
 			nblocks_out, stream, NULL);
 }
@@ -1572,7 +1593,17 @@ int xzamd_encode_device_(xzamd_ctx *c,
 		c->resume.stride = XZAMD_RESUME_BYTES(J.m.model_slots); c->resume.nrec = J.rec_done;
 		c->resume.nblocks = J.total_blocks; c->resume.block_size = J.block_size; c->resume.in_size = in_size;
 	}
-	if (rc == XZAMD_OK && J.repair) {
+	if (rc == XZAMD_OK && J.segments && J.verify) {
+		/* the segments of a single-Block Stream: verdicts on their chains, and with XZAMD_F_REPAIR the rejected ones replaced */
+		uint64_t ns = J.opos;
+		rc = xzamd_chains_encoded_(c, J.d_out, J.opos, J.out_cap, J.d_in, in_size, J.opt, J.check, J.repair, J.binfo, J.total_blocks,
+				&ns, J.st);
+		if (rc == XZAMD_OK) {
+			*out_size = ns;
+			c->stats.out_bytes = ns;
+		}
+		c->stats.ms_verify = c->report.ms_verify;
+	} else if (rc == XZAMD_OK && J.repair) {
 		/* verified and repaired encode: per-Block verdicts; the Blocks the device decoder rejects are re-encoded and spliced */
 		uint64_t ns = J.opos;
 		rc = xzamd_repair_encoded_(c, J.d_out, J.opos, J.out_cap, J.d_in, in_size, J.block_size, J.opt, J.check, J.whole, J.binfo,

@@ -56,6 +56,7 @@ typedef struct {
 	uint8_t *steps;                 /* optional: nb bytes */
 	int plain_history;              /* with d_expected: it is only compared with; the units are those of a decode without it (dictionary
 	                                 * resets, history = the output itself) */
+	int chains;                     /* hb names bare chunk chains (xzamd_chains.c): the scan is xzk_dec_scan_chains, every other stage as it is */
 } xzamd_dec_job;
 
 /* The resume table a context keeps of its last encode with XZAMD_F_KEEP_RESUME / XZAMD_F_VERIFY (xzamd_host.c) */
@@ -93,6 +94,9 @@ int xzamd_stream_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, xza
 #define XZAMD_VT_PRECISE 2
 int xzamd_verify_table_(xzamd_ctx *c, const uint8_t *d_xz, uint64_t xz_size, const xzamd_hdr_rec *recs, uint64_t nb, int check,
 		const uint8_t *d_original, uint64_t original_size, int mode, uint8_t *steps, xzamd_verify_report *report, void *stream);
+/* The collecting run of a prepared job (job->steps set, utotal = the sum of its uncompressed sizes) as xzamd_verify_table_ makes
+ * it: the kept table when it fits (XZAMD_VT_KEPT), the second look at "decode" / "check" verdicts (XZAMD_VT_PRECISE) */
+int xzamd_verify_job_(xzamd_ctx *c, void *st, xzamd_dec_job *job, uint64_t utotal, int mode, xzamd_verify_report *rp);
 /* What an encode on the context would overwrite while a repair re-encodes Blocks on it: the kept resume table (taken out of
  * the context, so that the re-encode neither frees nor replaces it) and the stats of the call being repaired */
 typedef struct {
@@ -140,6 +144,44 @@ typedef struct {
  * Stream Footer follow the last Block.  Returns XZAMD_OK, XZAMD_MEM_ERROR or XZAMD_PROG_ERROR (a table that is not adjacent). */
 int xzamd_repair_plan_(xzamd_rp_block *blocks, uint64_t nb, int check, int framed, xzamd_rp_plan *plan);
 void xzamd_repair_plan_free_(xzamd_rp_plan *plan);
+
+/* ---- bare chunk chains: the segments of a single-Block Stream (xzamd_chains.c; DESIGN.md 3.6 "Chains") ---- */
+/* The splice layout of a chain repair (xzamd_repair_plan.c): chains lie back to back (pos[i + 1] = pos[i] + len[i]), every chain
+ * behind the first replaced one moves, nothing else is written -- no header, padding, Check, Index or Footer.  CODED: the
+ * re-encoded chain lies at scratch offset src, new_len bytes.  STORED: 0x01 + 64 KiB of the original, then 0x02 chunks, no end
+ * marker; new_len is computed.  The plan's segment kinds and destinations are those of xzamd_repair_plan_. */
+typedef struct {
+	uint64_t pos;           /* in: of the chain's first byte */
+	uint64_t len;           /* in: its old length */
+	uint64_t usize;         /* in */
+	uint64_t uoff;          /* in: of the segment's first byte in the original */
+	uint32_t repl;          /* in: XZAMD_RP_* */
+	uint32_t pad_;
+	uint64_t src;           /* in, CODED */
+	uint64_t new_len;       /* CODED: in; KEEP, STORED: out */
+	uint64_t new_pos;       /* out */
+} xzamd_cp_chain;
+int xzamd_chains_plan_(xzamd_cp_chain *chains, uint64_t n, xzamd_rp_plan *plan);
+/* The collecting verification of the chains binfo names inside d_chains (binfo as XZAMD_F_SEGMENTS fills it in): steps[i] =
+ * XZAMD_VSTEP_* of segment i.  mode: XZAMD_VT_*.  XZAMD_OK / XZAMD_DATA_ERROR / a failure of the call. */
+int xzamd_chains_verify_(xzamd_ctx *c, const uint8_t *d_chains, uint64_t size, const xzamd_block_info *binfo, uint64_t nseg,
+		uint32_t dict_size, int check, const uint8_t *d_original, uint64_t original_size, int mode, uint8_t *steps,
+		xzamd_verify_report *rp, void *st);
+/* XZAMD_F_VERIFY / XZAMD_F_REPAIR on behalf of an XZAMD_F_SEGMENTS encode, which the batch encoder refers to weakly: verdicts
+ * on the chains just written to d_out, and with `repair` the replacement of the rejected ones (binfo and *new_size rewritten) */
+int xzamd_chains_encoded_(xzamd_ctx *c, void *d_out, uint64_t size, uint64_t cap, const void *d_in, uint64_t in_size,
+		const xzamd_lzma_options *opt, int check, int repair, xzamd_block_info *binfo, uint64_t nseg, uint64_t *new_size, void *stream);
+/* XZAMD_F_SINGLE on behalf of xzamd_stream_encode_device (weak reference): the framed single-Block Stream */
+int xzamd_single_encode_(xzamd_ctx *c, const void *d_in, uint64_t in_size, uint64_t block_size, const xzamd_lzma_options *opt,
+		int check, uint32_t flags, void *d_out, uint64_t out_cap, uint64_t *out_size, xzamd_block_info *binfo, uint64_t binfo_cap,
+		uint64_t *nsegments, void *stream);
+/* Internal flag of xzamd_encode_device_ (xzamd_stream_encode_device refuses it): with XZAMD_F_SEGMENTS, the flags
+ * XZAMD_F_KEEP_RESUME / _VERIFY / _REPAIR are allowed and act on the chains (xzamd_chains_encoded_) */
+#define XZAMD_F_CHAINS_ 0x80000000u
+/* xzamd_repair.c: what the Block repair and the chain repair share */
+void xzamd_repair_rung1_options_(const xzamd_lzma_options *opt, xzamd_lzma_options *o);
+void xzamd_repair_knob_reject_(uint8_t *steps, uint64_t n);
+int xzamd_repair_knob_rung2_(void);
 
 double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt);   /* device work buffers per input byte of a batch */
 

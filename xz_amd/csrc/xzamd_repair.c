@@ -34,7 +34,7 @@ static double ms_between(const struct timespec *a, const struct timespec *b)
 #define HIPR(call, msg) do { if (call) FAILR(XZAMD_DEVICE_ERROR, msg); } while (0)
 
 /* XZAMD_TEST_REPAIR_REJECT="0,2" (tests): the first pass treats these Blocks as rejected at step "decode" */
-static void knob_reject(uint8_t *steps, uint64_t nb)
+void xzamd_repair_knob_reject_(uint8_t *steps, uint64_t nb)
 {
 	const char *e = getenv("XZAMD_TEST_REPAIR_REJECT");
 	while (e && *e) {
@@ -48,7 +48,7 @@ static void knob_reject(uint8_t *steps, uint64_t nb)
 }
 
 /* XZAMD_TEST_REPAIR_RUNG=2 (tests): what rung 1 made counts as rejected, so the stored rung runs */
-static int knob_rung2(void)
+int xzamd_repair_knob_rung2_(void)
 {
 	const char *e = getenv("XZAMD_TEST_REPAIR_RUNG");
 	return e && *e == '2';
@@ -60,7 +60,7 @@ static uint64_t slot_bytes(uint64_t usize)
 	return (xzamd_block_buffer_bound(usize < RUNG1_MIN_BLOCK ? RUNG1_MIN_BLOCK : usize) + 15) & ~15ull;
 }
 
-static void rung1_options(const xzamd_lzma_options *opt, xzamd_lzma_options *o)
+void xzamd_repair_rung1_options_(const xzamd_lzma_options *opt, xzamd_lzma_options *o)
 {
 	*o = *opt;
 	if (o->span_size == XZAMD_SPAN_DEFAULT || o->span_size == XZAMD_SPAN_AUTO)
@@ -123,7 +123,7 @@ static int repair_run_(xzamd_ctx *c, uint8_t *d_xz, uint64_t size, uint64_t cap,
 	R->passes = 1;
 	R->ms_verify_passes = rp->ms_verify;
 	if (rc != XZAMD_OK && rc != XZAMD_DATA_ERROR) goto done;
-	knob_reject(steps, nb);
+	xzamd_repair_knob_reject_(steps, nb);
 	for (uint64_t b = 0; b < nb; ++b) nbad += steps[b] != XZAMD_VSTEP_NONE;
 	R->blocks_bad = nbad;
 	if (nbad == 0) goto done;       /* all good (XZAMD_OK), or a defect no Block carries (the sizes of Stream and original differ) */
@@ -158,9 +158,9 @@ static int repair_run_(xzamd_ctx *c, uint8_t *d_xz, uint64_t size, uint64_t cap,
 	have_saved = 1;
 	{
 		xzamd_lzma_options o1;
-		const int force2 = knob_rung2();
+		const int force2 = xzamd_repair_knob_rung2_();
 		double ms_v = 0;
-		rung1_options(opt, &o1);
+		xzamd_repair_rung1_options_(opt, &o1);
 		for (uint64_t b = 0; b < nb; ) {
 			if (steps[b] == XZAMD_VSTEP_NONE) { ++b; continue; }
 			if (recs[b].usize == 0) {

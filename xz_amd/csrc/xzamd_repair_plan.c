@@ -141,3 +141,53 @@ int xzamd_repair_plan_(xzamd_rp_block *blocks, uint64_t nb, int check, int frame
 	plan->new_size = plan->tail_pos + opos;
 	return XZAMD_OK;
 }
+
+/* The splice layout of a chain repair: the segments of a single-Block Stream are bare LZMA2 chunk chains that lie back to back,
+ * so a replaced chain only shifts the ones behind it.  Same plan structure, same segment kinds, destinations from tail_pos. */
+int xzamd_chains_plan_(xzamd_cp_chain *chains, uint64_t n, xzamd_rp_plan *plan)
+{
+	builder B = { plan, 0, 0, 0 };
+	memset(plan, 0, sizeof(*plan));
+	plan->first = n;
+	for (uint64_t i = 0; i < n; ++i) {
+		if (i + 1 < n && chains[i + 1].pos != chains[i].pos + chains[i].len)
+			return XZAMD_PROG_ERROR;
+		if (chains[i].repl != XZAMD_RP_KEEP && plan->first == n) plan->first = i;
+		if (chains[i].repl == XZAMD_RP_KEEP) chains[i].new_len = chains[i].len;
+		chains[i].new_pos = chains[i].pos;
+	}
+	if (plan->first == n) return XZAMD_OK;
+	plan->tail_pos = chains[plan->first].pos;
+
+	uint64_t opos = 0;              /* offset from tail_pos */
+	for (uint64_t i = plan->first; i < n; ++i) {
+		xzamd_cp_chain *K = &chains[i];
+		K->new_pos = plan->tail_pos + opos;
+		if (K->repl == XZAMD_RP_KEEP || K->repl == XZAMD_RP_CODED) {
+			const uint32_t kind = K->repl == XZAMD_RP_KEEP ? 2u : 0u;
+			const uint64_t from = K->repl == XZAMD_RP_KEEP ? K->pos : K->src;
+			for (uint64_t o = 0; o < K->new_len; o += XZAMD_RP_SEG_MAX)
+				seg_put(&B, kind, from + o, K->new_len - o < XZAMD_RP_SEG_MAX ? K->new_len - o : XZAMD_RP_SEG_MAX, opos + o);
+			opos += K->new_len;
+		} else if (K->repl == XZAMD_RP_STORED) {
+			/* the stored chain as the batch encoder writes it for a segment that does not shrink: 0x01 + 64 KiB of the original,
+			 * then 0x02 chunks; no end marker (the Block's own follows the last chain) */
+			const uint64_t start = opos;
+			uint8_t ctl = 0x01;
+			for (uint64_t ip = 0; ip < K->usize; ip += 65536) {
+				const uint64_t cs = K->usize - ip < 65536 ? K->usize - ip : 65536;
+				const uint8_t ch[3] = { ctl, (uint8_t)((cs - 1) >> 8), (uint8_t)(cs - 1) };
+				ctl = 0x02;
+				(void)lit_put(&B, ch, 3, opos);
+				seg_put(&B, 3, K->uoff + ip, cs, opos + 3);
+				opos += 3 + cs;
+			}
+			K->new_len = opos - start;
+		} else
+			return xzamd_repair_plan_free_(plan), XZAMD_PROG_ERROR;
+	}
+	if (B.oom) return xzamd_repair_plan_free_(plan), XZAMD_MEM_ERROR;
+	plan->tail_len = opos;
+	plan->new_size = plan->tail_pos + opos;
+	return XZAMD_OK;
+}

@@ -138,8 +138,8 @@ struct lzma_internal_s {
 	int blk_open;                /* Block Header handed to the output queue, end of the Block not yet */
 	uint64_t blk_csize, blk_usize, blk_crc;       /* of the open Block: chunk chains so far, their input, its Check so far */
 	uint64_t segment_env;        /* XZAMD_SEGMENT_KIB << 10, 0 = lzma_mt_block_size of the chain */
-	int repair;                  /* XZAMD_REPAIR=1 (read at init; MT layout only): every job runs with XZAMD_F_REPAIR and is finished
-	                              * before the next one is launched */
+	int repair;                  /* XZAMD_REPAIR=1 (read at init): every job runs with XZAMD_F_REPAIR -- on its Blocks, or in single mode on
+	                              * the chains of its segments -- and is finished before the next one is launched */
 };
 
 static void *a_alloc(const lzma_allocator *a, size_t n)
@@ -298,6 +298,10 @@ static lzma_ret grow_pinned(uint8_t **buf, uint64_t *cap, uint64_t keep, uint64_
 }
 
 static void vlog(const char *what, const job *j);
+/* (xzamd_chains.c, referred to weakly: without it XZAMD_REPAIR is not honoured in single mode) */
+extern int xzamd_chains_encoded_(xzamd_ctx *c, void *d_out, uint64_t size, uint64_t cap, const void *d_in, uint64_t in_size,
+		const xzamd_lzma_options *opt, int check, int repair, xzamd_block_info *binfo, uint64_t nseg, uint64_t *new_size,
+		void *stream) __attribute__((weak));
 
 /* worker_encode() x nblocks (stream_encoder_mt.c:219-361) for one job on one GPU, in two steps.  job_launch: buffers, upload,
  * device encode -- which may come back DEFERRED: everything of the job is launched, the back end of its last batch still runs
@@ -346,7 +350,7 @@ static lzma_ret job_launch(lzma_internal *in, devslot *d, job *j, int io, int *r
 	void *cs = xzamd_ctx_stream_(d->ctx);
 	if (!injected && !(xzk_h2d(b->d_in, j->stage, n, cs) || xzk_sync(cs)) && (vlog("uploaded", j), 1))
 		*rc_out = xzamd_encode_device_(d->ctx, b->d_in, n, in->block_size, &j->opt, in->check,
-				in->single ? XZAMD_F_SEGMENTS : in->repair ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_REPAIR : XZAMD_F_BLOCKS_ONLY,
+				in->single ? (in->repair ? XZAMD_F_SEGMENTS | XZAMD_F_CHAINS_ | XZAMD_F_REPAIR : XZAMD_F_SEGMENTS) : in->repair ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_REPAIR : XZAMD_F_BLOCKS_ONLY,
 				b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
 				&j->nblocks, NULL, ((nd && *nd == '1') || in->repair) ? NULL : deferred);
 	return LZMA_OK;
@@ -682,7 +686,8 @@ static lzma_ret encoder_init(lzma_stream *strm, lzma_ret r, const xzamd_lzma_opt
 	in->segment_env = segment_env;
 	{
 		const char *rp = getenv("XZAMD_REPAIR");
-		in->repair = !single && rp && *rp == '1';
+		/* (single mode: the chains of the segments are what is verified and replaced -- with the unit that does it) */
+		in->repair = rp && *rp == '1' && (!single || xzamd_chains_encoded_ != NULL);
 	}
 	in->sequence = ISEQ_RUN;
 	in->sseq = SEQ_HEADER;

@@ -465,6 +465,41 @@ int xzamd_file_decode_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size,
 int xzamd_file_decode_range_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, uint64_t uoffset, uint64_t ulen,
 		void *d_out, uint64_t out_cap, uint64_t *out_size, uint64_t *blocks_decoded, void *stream);
 
+/* ---- forward decode: a file read from its front, without its Index ----
+ * xzamd_file_decode_device needs the last byte of a file before it can decode the first.  This entry reads as the
+ * reference's lzma_stream_decoder does (common/stream_decoder.c, index_hash.c): Stream Header, then Block after Block -- a
+ * kernel of one wavefront finds them, by the sizes in their headers or, where a header has none, by walking the LZMA2
+ * chunk headers -- and only then the Index and the Stream Footer, which must be exactly what these Blocks call for.  So a
+ * truncated file, or one that is damaged in or behind a Block, decodes as far as its last whole good Block:
+ *   XZAMD_OK          the whole input was read (without XZAMD_FWD_CONCATENATED: up to the end of the first Stream;
+ *                     report->consumed tells where that is)
+ *   XZAMD_BUF_ERROR   the input ends early (report->stop = XZAMD_FWD_TRUNCATED: every complete Block in front of the end is
+ *                     delivered, a partial last Block is not), or out_cap is too small (XZAMD_FWD_OUT_FULL: the Blocks that
+ *                     fit are delivered)
+ *   any other code    that of the first defect (report->stop = XZAMD_FWD_DEFECT, report->code / step); the Blocks in front
+ *                     of it are delivered, their Checks verified
+ * *out_size = the bytes delivered at d_out, whatever the code.  Codes as xzamd_file_decode_device gives them, but 7
+ * (LZMA_FORMAT_ERROR) only for twelve first bytes without the Header Magic.  One walk launch and a constant number of small
+ * reads per Stream, whatever its Block count. */
+#define XZAMD_FWD_CONCATENATED 1u   /* read Stream Padding and further Streams (LZMA_CONCATENATED) */
+#define XZAMD_FWD_END 1u
+#define XZAMD_FWD_TRUNCATED 2u
+#define XZAMD_FWD_DEFECT 3u
+#define XZAMD_FWD_OUT_FULL 4u
+typedef struct {
+	uint64_t streams;               /* Streams read to the end of their Footer */
+	uint64_t blocks;                /* Blocks met whole */
+	uint64_t blocks_delivered;      /* ... of them decoded, verified and counted in *out_size */
+	uint64_t consumed;              /* bytes of the input dealt with */
+	uint64_t stop_offset;           /* of the Block or framing piece the read stopped at */
+	uint32_t stop;                  /* XZAMD_FWD_* */
+	uint32_t code;                  /* XZAMD_FWD_DEFECT: the code returned */
+	uint32_t step;                  /* ... and, for a defect of a Block Header or chunk chain, which check failed */
+	uint32_t reserved_;
+} xzamd_forward_report;
+int xzamd_file_decode_forward_device(xzamd_ctx *ctx, const void *d_xz, uint64_t xz_size, uint32_t flags,
+		void *d_out, uint64_t out_cap, uint64_t *out_size, xzamd_forward_report *report, void *stream);
+
 /* Host-side framing helpers for the multi-GPU path: Stream Header (12 bytes),
  * Index + Stream Footer from gathered Block records. Return bytes written. */
 uint64_t xzamd_frame_header(uint8_t *out, int check);

@@ -154,6 +154,14 @@ typedef struct {
 	void *reserved_ptr1, *reserved_ptr2, *reserved_ptr3, *reserved_ptr4;
 } lzma_mt;
 
+/* api/lzma/container.h:534-609: flags of the decoders */
+#define LZMA_TELL_NO_CHECK UINT32_C(0x01)
+#define LZMA_TELL_UNSUPPORTED_CHECK UINT32_C(0x02)
+#define LZMA_TELL_ANY_CHECK UINT32_C(0x04)
+#define LZMA_CONCATENATED UINT32_C(0x08)
+#define LZMA_IGNORE_CHECK UINT32_C(0x10)
+#define LZMA_FAIL_FAST UINT32_C(0x20)
+
 #endif /* LZMA_H */
 
 lzma_ret lzma_stream_encoder_mt(lzma_stream *strm, const lzma_mt *options);
@@ -187,6 +195,25 @@ lzma_ret lzma_stream_buffer_encode(lzma_filter *filters, lzma_check check, const
 		const uint8_t *in, size_t in_size, uint8_t *out, size_t *out_pos, size_t out_size);
 lzma_ret lzma_easy_buffer_encode(uint32_t preset, lzma_check check, const lzma_allocator *allocator,
 		const uint8_t *in, size_t in_size, uint8_t *out, size_t *out_pos, size_t out_size);
+
+/* The .xz Stream decoder (common/stream_decoder.c:443, stream_decoder_mt.c:1951, stream_buffer_decoder.c:15, common.c:437),
+ * driven through the same lzma_code / lzma_end / lzma_get_progress: the forward reader of the device decoder behind a coder
+ * that stages input in batches (XZAMD_DEC_BATCH_KIB, default 512 MiB), decodes every whole Block of a batch on the device and
+ * drains the decoded bytes through next_out.  Output bytes and final codes are liblzma's; the sequence of calls in which
+ * they arrive is not (the coder batches), and the bytes of a partial last Block of a truncated input are not delivered.
+ * flags: LZMA_TELL_NO_CHECK / _UNSUPPORTED_CHECK / _ANY_CHECK (once per Stream), LZMA_CONCATENATED; LZMA_FAIL_FAST is
+ * accepted; LZMA_IGNORE_CHECK is declined with LZMA_OPTIONS_ERROR.  lzma_stream_decoder_mt uses flags and memlimit_stop of
+ * lzma_mt; threads and timeout are accepted and unused.
+ * Without LZMA_CONCATENATED, input behind the end of the Stream is left with the caller (next_in / avail_in / total_in as
+ * liblzma leaves them) only as far as the lzma_code call that reaches the end handed it in: bytes that EARLIER calls handed
+ * in have been copied into the staging and count as consumed, so on a piecewise feed total_in can exceed the Stream's length
+ * by up to a batch.  A client that needs the exact end feeds the file in one call, or uses lzma_stream_buffer_decode.
+ * INTEGRATION.md section 5 has the full list. */
+lzma_ret lzma_stream_decoder(lzma_stream *strm, uint64_t memlimit, uint32_t flags);
+lzma_ret lzma_stream_decoder_mt(lzma_stream *strm, const lzma_mt *options);
+lzma_ret lzma_stream_buffer_decode(uint64_t *memlimit, uint32_t flags, const lzma_allocator *allocator, const uint8_t *in,
+		size_t *in_pos, size_t in_size, uint8_t *out, size_t *out_pos, size_t out_size);
+lzma_check lzma_get_check(const lzma_stream *strm);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,16 @@ class RepairReport(C.Structure):
                 ("ms_reencode", C.c_float), ("ms_splice", C.c_float), ("reserved_", C.c_uint32)]
 
 
+class ForwardReport(C.Structure):
+    """xzamd_forward_report: how far a forward decode read and why it stopped."""
+    _fields_ = [(n, C.c_uint64) for n in ("streams", "blocks", "blocks_delivered", "consumed", "stop_offset")] + \
+               [(n, C.c_uint32) for n in ("stop", "code", "step", "reserved_")]
+
+
+FWD_CONCATENATED = 1
+FWD_END, FWD_TRUNCATED, FWD_DEFECT, FWD_OUT_FULL = 1, 2, 3, 4
+
+
 class BlockInfo(C.Structure):
     _fields_ = [("unpadded_size", C.c_uint64), ("uncompressed_size", C.c_uint64),
                 ("out_offset", C.c_uint64), ("total_size", C.c_uint64)]
@@ -144,6 +154,11 @@ def lib():
                                                          C.POINTER(C.c_uint64), C.c_void_p]
             l.xzamd_debug_file_counters_.restype = None
             l.xzamd_debug_file_counters_.argtypes = [C.POINTER(C.c_uint64)]
+        if hasattr(l, "xzamd_file_decode_forward_device"):   # (an older library lacks the forward reader)
+            l.xzamd_file_decode_forward_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                           C.POINTER(C.c_uint64), C.POINTER(ForwardReport), C.c_void_p]
+            l.xzamd_debug_forward_counters_.restype = None
+            l.xzamd_debug_forward_counters_.argtypes = [C.POINTER(C.c_uint64)]
         if hasattr(l, "xzamd_crc32_combine"):           # (an older library lacks the single-Block encoder)
             l.xzamd_crc32_combine.restype = C.c_uint32
             l.xzamd_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
@@ -227,9 +242,11 @@ def corpus_tar(n, roots=TAR_ROOTS, seed=1):
 class XzAmdError(RuntimeError):
     """`code` = the XZAMD_* / lzma_ret value of the failed call, where there is one."""
 
-    def __init__(self, msg, code=None):
+    def __init__(self, msg, code=None, partial=None, report=None):
         super().__init__(msg)
         self.code = code
+        self.partial = partial      # decode_forward: the bytes in front of the defect
+        self.report = report        # ... and its report
 
 
 def _stream_dict(s):
@@ -583,6 +600,34 @@ class Encoder:
         if rc != 0:
             raise XzAmdError(f"xzamd_file_decode_range_device failed ({rc})" + self._detail(), rc)
         return out[: osz.value], nb.value
+
+    def decode_forward(self, xz, out_cap, concatenated=True):
+        """Decode an .xz file held in a CUDA uint8 tensor from its front, without its Index (xzamd_file_decode_forward_device):
+        a truncated file, or one damaged in or behind a Block, gives every whole good Block in front of the damage.
+        Returns (decoded tensor view, report dict: the fields of xzamd_forward_report).  A truncated input and an output
+        that does not fit are no exceptions: report["code"] is then XZAMD_BUF_ERROR (10) and report["stop"] tells which.
+        Any other code raises XzAmdError, whose .partial / .report carry the bytes in front of the defect and the report."""
+        import torch
+        assert xz.is_cuda and xz.dtype == torch.uint8 and xz.is_contiguous()
+        out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=xz.device)
+        osz, rp = C.c_uint64(0), ForwardReport()
+        torch.cuda.current_stream(xz.device).synchronize()
+        rc = lib().xzamd_file_decode_forward_device(
+            self._ctx, C.c_void_p(xz.data_ptr()) if xz.numel() else None, xz.numel(), FWD_CONCATENATED if concatenated else 0,
+            C.c_void_p(out.data_ptr()), out_cap, C.byref(osz), C.byref(rp), None)
+        report = {n: getattr(rp, n) for n in ("streams", "blocks", "blocks_delivered", "consumed", "stop_offset", "stop", "step")}
+        report["code"] = rc
+        if rc not in (0, 10):
+            raise XzAmdError(f"xzamd_file_decode_forward_device failed ({rc})" + self._detail(), rc, out[: osz.value], report)
+        return out[: osz.value], report
+
+    @staticmethod
+    def debug_forward_counters():
+        """Counts of the last decode_forward (test instrumentation): (device-to-host reads, kernel-launch calls, Blocks
+        delivered, walk launches)."""
+        a = (C.c_uint64 * 4)()
+        lib().xzamd_debug_forward_counters_(a)
+        return tuple(a)
 
     # debug hooks used by the parity tests
     @staticmethod

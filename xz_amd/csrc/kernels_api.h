@@ -341,6 +341,27 @@ typedef struct {
 /* every record must have hpos <= end <= xz_size: the kernel bounds its reads by `end` */
 int xzk_dec_headers(const uint8_t *d_xz, uint64_t xz_size, const xzamd_hdr_rec *d_recs, uint32_t nblocks, void *d_table, void *stream);
 
+/* ---- the forward walk: the Blocks of one Stream found from the front, without its Index (k_dec_walk, lzma_decode.hip) ----
+ * One wavefront follows the dependent chain Block Header -> sizes -> next Block Header (xzw_walk, xzamd_walk_parse.h): a
+ * Block whose header holds both sizes is one hop, any other one hop per LZMA2 chunk.  d_rows receives one row per Block
+ * that lies whole inside [0, size) (`end` = 0: the host fills it in), d_res why and where the walk stopped. */
+#define XZAMD_WALK_INDEX 1u         /* the Index Indicator stands at res.pos */
+#define XZAMD_WALK_INCOMPLETE 2u    /* the bytes end inside the header, chain, padding or Check of the Block at res.pos */
+#define XZAMD_WALK_TABLE_FULL 3u    /* `cap` rows written: launch again from res.pos / res.upos */
+#define XZAMD_WALK_DEFECT 4u        /* res.code (XZB_DATA_ERROR / XZB_OPTIONS_ERROR) and res.step (XZB_S_*) of the Block at res.pos */
+typedef struct {
+	uint32_t stop;       /* XZAMD_WALK_* */
+	uint32_t code, step;
+	uint32_t nrows;      /* rows written */
+	uint64_t pos;        /* offset of the Block Header (or Index Indicator) the walk stopped at */
+	uint64_t upos;       /* where that Block's output would go */
+	uint64_t hops;       /* dependent loads taken: Block Headers + chunk headers */
+	uint64_t pad_;
+} xzamd_walk_result;
+/* pos0 <= size; csz = size of the Stream's Check; cap >= 1 */
+int xzk_dec_walk(const uint8_t *d_xz, uint64_t size, uint64_t pos0, uint32_t csz, uint64_t upos0, xzamd_hdr_rec *d_rows,
+		uint32_t cap, xzamd_walk_result *d_res, void *stream);
+
 int xzk_d2d(void *dst, const void *src, uint64_t bytes, void *stream);
 int xzk_malloc(void **p, uint64_t bytes);
 int xzk_free(void *p);

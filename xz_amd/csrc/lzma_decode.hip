@@ -26,6 +26,7 @@
 #include "wave.h"
 #include "bcj_rules.h"
 #include "xzamd_block_parse.h"
+#include "xzamd_walk_parse.h"
 
 namespace {
 
@@ -172,6 +173,18 @@ __global__ __launch_bounds__(64) void k_dec_headers(const uint8_t* __restrict__ 
     chains[b] = ch;
     errs[b].code = code;
     errs[b].step = step;
+}
+
+// The forward walk: the Block table of one Stream without its Index (xzw_walk, xzamd_walk_parse.h: the text the CPU harness
+// runs too).  Header -> sizes -> next header is a dependent chain, so one wavefront is all that can be spent on it: every
+// lane follows the same addresses, the loaded header bytes are made wave-uniform (readfirstlane) so that the branches are
+// scalar, and lane 0 alone stores the rows and the result with plain vector stores.  About one HBM-miss load per hop: a Block
+// with both sizes in its header is one hop, any other one hop per LZMA2 chunk.  No atomics, no waits on other wavefronts;
+// every read is bounded by `size`, and each iteration moves its offset forward, so the walk ends after at most `size` steps.
+__global__ __launch_bounds__(64) void k_dec_walk(const uint8_t* __restrict__ xz, uint64_t size, uint64_t pos0, uint32_t csz,
+        uint64_t upos0, xzamd_hdr_rec* __restrict__ rows, uint32_t cap, xzamd_walk_result* __restrict__ res)
+{
+    xzw_walk(xz, size, pos0, csz, upos0, rows, cap, res);
 }
 
 // ---- range decoder + LZMA symbol decoder, wave-uniform -------------------------------------------------
@@ -1060,6 +1073,14 @@ int xzk_dec_headers(const uint8_t* d_xz, uint64_t xz_size, const xzamd_hdr_rec* 
     xzamd_hdr_err* errs = (xzamd_hdr_err*)(stored + (uint64_t)nblocks * XZAMD_HDR_CHECK_BYTES);
     hipLaunchKernelGGL(k_dec_headers, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)stream_, d_xz, xz_size, d_recs, nblocks,
             blocks, chains, stored, errs);
+    return (int)hipGetLastError();
+}
+
+int xzk_dec_walk(const uint8_t* d_xz, uint64_t size, uint64_t pos0, uint32_t csz, uint64_t upos0, xzamd_hdr_rec* d_rows, uint32_t cap,
+        xzamd_walk_result* d_res, void* stream_)
+{
+    if (!d_xz || !d_rows || !d_res || cap == 0 || pos0 > size) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dec_walk, dim3(1), dim3(64), 0, (hipStream_t)stream_, d_xz, size, pos0, csz, upos0, d_rows, cap, d_res);
     return (int)hipGetLastError();
 }
 

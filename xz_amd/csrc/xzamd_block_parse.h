@@ -27,7 +27,9 @@ enum {
 	XZB_S_NONE = 0, XZB_S_BEYOND, XZB_S_INDICATOR, XZB_S_HEADER_SIZE, XZB_S_HEADER_CRC, XZB_S_RESERVED_FLAGS,
 	XZB_S_CSIZE_VLI, XZB_S_USIZE_VLI, XZB_S_FILTER_FLAGS, XZB_S_LZMA2_PROPS, XZB_S_DELTA_PROPS, XZB_S_BCJ_PROPS,
 	XZB_S_BCJ_START, XZB_S_FILTER_ID, XZB_S_HEADER_PADDING, XZB_S_CHAIN, XZB_S_UNPADDED, XZB_S_SIZES, XZB_S_BLOCK_END,
-	XZB_S_BLOCK_PADDING, XZB_S_TOO_LARGE, XZB_S_COUNT
+	XZB_S_BLOCK_PADDING, XZB_S_TOO_LARGE,
+	XZB_S_CHUNK_CONTROL, XZB_S_CHUNK_SIZES,         /* the forward walk over a chunk chain (xzamd_walk_parse.h) */
+	XZB_S_COUNT
 };
 
 XZB_FN int xzb_vli(const uint8_t *p, uint64_t n, uint64_t *pos, uint64_t *v)

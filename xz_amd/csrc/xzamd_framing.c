@@ -43,7 +43,8 @@ const char *xzamd_block_step_msg_(uint32_t step)
 		"BCJ filter with a non-zero start offset is not decoded on the device", "filter id the device decoder does not know",
 		"Block Header padding", "filter chain: LZMA2 must be the last filter and only the last",
 		"Unpadded Size smaller than its header", "Block Header sizes differ from the Index", "Block beyond the Index",
-		"Block Padding", "Block too large for the device decoder" };
+		"Block Padding", "Block too large for the device decoder", "LZMA2 chunk control byte",
+		"Block Header sizes differ from the LZMA2 chunk chain" };
 	return step < XZB_S_COUNT ? msg[step] : "";
 }
 
@@ -77,6 +78,12 @@ static int flags_read(const uint8_t f[2], int *check, const char **msg)
 	}
 	return 0;
 }
+
+/* the same primitives for the forward reader (xzamd_forward.c), which meets the pieces of a Stream in file order */
+int xzamd_fr_header_(const uint8_t h[12]) { return header_read(h); }
+int xzamd_fr_footer_(const uint8_t f[12], uint64_t *index_size) { return footer_read(f, index_size); }
+int xzamd_fr_flags_(const uint8_t f[2], int *check, const char **msg) { return flags_read(f, check, msg); }
+uint32_t xzamd_fr_check_size_(int check) { return check_sizes[check & 0x0F]; }
 
 #define WFAIL(code, m) do { rc = (code); *msg = (m); goto out; } while (0)
 #define WREAD(off, buf, n) do { if (xzamd_src_read_(s, (off), (buf), (n))) WFAIL(XZAMD_DEVICE_ERROR, "d2h container framing"); } while (0)

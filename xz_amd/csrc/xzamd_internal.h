@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/xz_amd.h"
+#include "../../include/xz_amd_lzma.h"
 #include "kernels_api.h"
 
 uint32_t xzamd_crc32_host_(const uint8_t *p, size_t n);
@@ -236,6 +237,67 @@ XZAMD_HIDDEN int xzamd_block_table_(xzamd_src *s, const xzamd_hdr_rec *recs, uin
 /* the code of the first bad Block of the table in file order (0: none) and the text of its defect */
 XZAMD_HIDDEN int xzamd_blocks_first_bad_(const xzamd_blocks *B, uint64_t n, const char **msg);
 XZAMD_HIDDEN void xzamd_blocks_free_(xzamd_blocks *B);
+
+/* the primitives of the framing reader: 0, or 1 = bad magic bytes, 2 = bad CRC32 (Stream Header, Stream Footer); Stream Flags
+ * -> the Check, or XZAMD_OPTIONS_ERROR / XZAMD_UNSUPPORTED_CHECK with *msg; the size of a Check */
+#define XZAMD_FR_MAGIC 1
+#define XZAMD_FR_CRC 2
+XZAMD_HIDDEN int xzamd_fr_header_(const uint8_t h[12]);
+XZAMD_HIDDEN int xzamd_fr_footer_(const uint8_t f[12], uint64_t *index_size);
+XZAMD_HIDDEN int xzamd_fr_flags_(const uint8_t f[2], int *check, const char **msg);
+XZAMD_HIDDEN uint32_t xzamd_fr_check_size_(int check);
+
+/* xzamd_forward.c: the forward framing reader (DESIGN.md 3.6 "Forward reading").  One resumable step over the bytes of a
+ * file that are there so far: d_buf[0 .. size) continues the file at the first byte the steps before did not consume.
+ * A step reads Stream Headers, walks Blocks (xzk_dec_walk), decodes the whole ones into d_out (Checks verified), checks Index
+ * and Footer against the Blocks it met and passes Stream Padding, until the bytes or the room end.  It sets
+ *   consumed    bytes of d_buf that are dealt with for good: the next step's buffer starts behind them
+ *   produced    bytes written at d_out (the Blocks in front of a defect included, nothing behind it)
+ *   stop        XZAMD_FWD_MORE: more input is needed (never with `final`); XZAMD_FWD_END; XZAMD_FWD_TRUNCATED (`final` only);
+ *               XZAMD_FWD_OUT_FULL: the next Block does not fit behind `produced` (need: its size); XZAMD_FWD_DEFECT: code / step;
+ *               XZAMD_FWD_PAUSE (with pause_at_header only): the next byte is the first of a further Stream Header
+ * and returns XZAMD_OK unless the call itself failed (device, memory) or stop is XZAMD_FWD_DEFECT: then the defect's code. */
+#define XZAMD_FWD_MORE 0u
+#define XZAMD_FWD_PAUSE 5u
+#define XZAMD_FWD_PHASE_HEADER 0u   /* xzamd_forward_state.phase: the next byte is the first of a Stream Header */
+typedef struct {
+	uint32_t phase;                 /* XZF_* (xzamd_forward.c) */
+	uint32_t flags;                 /* XZAMD_FWD_CONCATENATED */
+	int check;                      /* of the Stream being read */
+	int first_stream;
+	uint64_t *unp, *usz;            /* Unpadded Size and Uncompressed Size of the Stream's Blocks so far */
+	uint64_t npairs, pairs_cap;
+	uint64_t padding;               /* Stream Padding bytes passed so far */
+	uint32_t walk_cap;              /* rows per walk launch (0: XZAMD_FWD_WALK_CAP) */
+	uint32_t pause_at_header;       /* stop with XZAMD_FWD_PAUSE in front of every Stream Header but the first */
+	/* totals over all steps */
+	uint64_t offset;                /* file offset of the next step's d_buf[0] */
+	uint64_t streams, blocks, blocks_delivered;
+	/* of the last step */
+	uint64_t consumed, produced, need;
+	uint32_t stop, code, step;
+	uint32_t pad2_;
+	uint64_t reads, launches, walks; /* device-to-host reads, kernel-launch calls, of them walk launches: totals */
+} xzamd_forward_state;
+#define XZAMD_FWD_WALK_CAP 4096u
+void xzamd_forward_init_(xzamd_forward_state *s, uint32_t flags);
+void xzamd_forward_free_(xzamd_forward_state *s);
+int xzamd_forward_step_(xzamd_ctx *c, xzamd_forward_state *s, const uint8_t *d_buf, uint64_t size, int final, uint8_t *d_out,
+		uint64_t out_cap, void *stream);
+/* test instrumentation of the last xzamd_file_decode_forward_device call: [0] device-to-host reads, [1] kernel-launch calls,
+ * [2] Blocks delivered, [3] walk launches */
+void xzamd_debug_forward_counters_(uint64_t out[4]);
+
+/* How lzma_code / lzma_end / lzma_get_progress (xzamd_stream.c) reach a coder that lives in another unit: the coder's internal
+ * struct starts with this, and `magic` tells it from the encoder's (XZAMD_MAGIC_DEC: the decoder of xzamd_decoder.c).  No call
+ * into that unit, so a program without it links as before. */
+#define XZAMD_MAGIC_DEC 0x585A414D44444543ull
+typedef struct {
+	uint64_t magic;
+	lzma_ret (*code)(lzma_stream *strm, lzma_action action);
+	void (*end)(lzma_stream *strm);
+	void (*progress)(lzma_stream *strm, uint64_t *progress_in, uint64_t *progress_out);
+} xzamd_coder_hooks;
 
 /* xzamd_options.c: the encode mode of an option set */
 typedef struct {

@@ -659,10 +659,8 @@ static lzma_ret encoder_init(lzma_stream *strm, lzma_ret r, const xzamd_lzma_opt
 	/* lzma_next_strm_init (common.h:401-410): re-initialising a stream replaces its coder, and an init that
 	 * fails ends the stream (lzma_end): a coder of ours must not survive in strm->internal -- an interposer
 	 * would hand it to the real liblzma next (preload.c), which would read it as its own lzma_internal */
-	if (strm->internal != NULL && strm->internal->magic == XZAMD_MAGIC) {
-		internal_free(strm->internal);
-		strm->internal = NULL;
-	}
+	if (strm->internal != NULL && (strm->internal->magic == XZAMD_MAGIC || strm->internal->magic == XZAMD_MAGIC_DEC))
+		lzma_end(strm);         /* (an encoder, or the decoder of xzamd_decoder.c through its hooks) */
 	if (r != LZMA_OK)
 		return r;
 	strm->internal = NULL;
@@ -1284,9 +1282,22 @@ lzma_ret lzma_filters_update(lzma_stream *strm, const lzma_filter *filters)
 	return LZMA_OK;
 }
 
+/* a coder of another unit (the decoder): reached through the hooks at the start of its internal struct */
+static const xzamd_coder_hooks *hooks_of(const lzma_stream *strm)
+{
+	return strm != NULL && strm->internal != NULL && strm->internal->magic == XZAMD_MAGIC_DEC
+			? (const xzamd_coder_hooks *)(const void *)strm->internal : NULL;
+}
+
 lzma_ret lzma_code(lzma_stream *strm, lzma_action action)
 {
 	/* common/common.c:203-376, restated for the one coder this library owns */
+	const xzamd_coder_hooks *hk = hooks_of(strm);
+	if (hk != NULL) {
+		if ((strm->next_in == NULL && strm->avail_in != 0) || (strm->next_out == NULL && strm->avail_out != 0))
+			return LZMA_PROG_ERROR;
+		return hk->code(strm, action);
+	}
 	if (strm == NULL || (strm->next_in == NULL && strm->avail_in != 0)
 			|| (strm->next_out == NULL && strm->avail_out != 0)
 			|| strm->internal == NULL || strm->internal->magic != XZAMD_MAGIC
@@ -1361,7 +1372,10 @@ lzma_ret lzma_code(lzma_stream *strm, lzma_action action)
 void lzma_end(lzma_stream *strm)
 {
 	if (strm != NULL && strm->internal != NULL) {
-		if (strm->internal->magic == XZAMD_MAGIC)
+		const xzamd_coder_hooks *hk = hooks_of(strm);
+		if (hk != NULL)
+			hk->end(strm);
+		else if (strm->internal->magic == XZAMD_MAGIC)
 			internal_free(strm->internal);
 		strm->internal = NULL;
 	}
@@ -1369,6 +1383,8 @@ void lzma_end(lzma_stream *strm)
 
 void lzma_get_progress(lzma_stream *strm, uint64_t *progress_in, uint64_t *progress_out)
 {
+	const xzamd_coder_hooks *hk = hooks_of(strm);
+	if (hk != NULL) { hk->progress(strm, progress_in, progress_out); return; }
 	if (strm && strm->internal && strm->internal->magic == XZAMD_MAGIC) {
 		lzma_internal *in = strm->internal;
 		/* stream_encoder_mt.c:1004-1024: what is finished plus how far every worker is inside its job -- here the share of

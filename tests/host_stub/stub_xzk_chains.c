@@ -38,7 +38,7 @@ int xzk_dec_scan_chains(const uint8_t *d_chains, xzamd_dec_block *d_blocks, uint
 				if (need_dict_reset) { err = 2; break; }
 				if (ctl >= 0xC0) {
 					if (c + 6 > B->csize) { err = 5; break; }
-					if (p[c + 5] > (4 * 5 + 4) * 9 + 8) { err = 4; break; }
+					if (p[c + 5] > (4 * 5 + 4) * 9 + 8 || (p[c + 5] % 45u) / 9u + p[c + 5] % 9u > 4u) { err = 4; break; }
 					hs = 6;
 					need_props = 0;
 				}

@@ -94,7 +94,9 @@ __global__ __launch_bounds__(64) void k_dec_scan(const uint8_t* __restrict__ xz,
             if (need_dict_reset) { err = DEC_NEED_DICT_RESET; break; }
             if (ctl >= 0xC0) {
                 if (c + 6 > B.csize) { err = DEC_TRUNCATED; break; }
-                if (p[c + 5] > (4 * 5 + 4) * 9 + 8) { err = DEC_BAD_PROPS; break; }
+                // lzma_lzma_lclppb_decode: (pb * 5 + lp) * 9 + lc, at most 224, and lc + lp <= 4 -- a properties byte no
+                // decoder takes is a defect of the chain's grammar, not of the data coded under it
+                if (p[c + 5] > (4 * 5 + 4) * 9 + 8 || (p[c + 5] % 45u) / 9u + p[c + 5] % 9u > 4u) { err = DEC_BAD_PROPS; break; }
                 hs = 6;
                 need_props = false;
             }

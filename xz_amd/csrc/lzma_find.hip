@@ -77,7 +77,9 @@ constexpr uint32_t SEED_RUNS = XZAMD_SEED_LEN / 256 + 1;
 constexpr uint32_t SN_WMAX = 5;
 
 // Suffix-neighbourhood finder (oracle: find_sn).  Both hot kernels of this path are bound by instruction
-// issue, not by memory, so the finder gives a position only the lanes it can use: a wavefront works on FOUR
+// issue, not by memory (this one, with the all-pairs filter it used to have: 115 vector instructions per position held
+// the SIMDs for 270 of a launch's 298 ms; DESIGN.md 3.2 has the figures with the row sort below), so
+// the finder gives a position only the lanes it can use: a wavefront works on FOUR
 // positions at once, one per DPP row of 16 lanes, and everything "uniform per position" lives in vector
 // registers (the scalar unit only runs the loop).  Lane roles inside a row, t = lane & 15, slot r = own slot:
 //   t =  0..4   slots r-1 .. r-5   (left neighbours, nearest first)
@@ -87,7 +89,9 @@ constexpr uint32_t SN_WMAX = 5;
 // A neighbour is eligible when it lies earlier in the same Block and inside the dictionary; it is a candidate
 // when it is more recent than every eligible neighbour nearer on its side ("recency record": exactly the
 // nodes BT4's descent would visit).  All candidates are compared with the text at x in parallel (16 bytes per
-// trip) and filtered by the Pareto rule with all-pairs compares inside the row (15 DPP row rotations).
+// trip) and filtered by the Pareto rule: the row's 16 candidates are sorted by distance (row_sort16: 10 DPP
+// compare-exchange layers) and a candidate stays when it is longer than everything sorted before it.  From the sort
+// on, a lane holds the entry of its rank in the row, not the candidate it fetched.
 // Row r of the wavefront at x0 owns positions x0 + 64 r .. x0 + 64 r + 63.  The loop is software pipelined
 // three deep: while position i is compared and filtered, the first 16 bytes of every candidate of i + 1 and
 // the window of i + 2 are in flight.
@@ -105,22 +109,66 @@ __device__ __forceinline__ uint32_t row_shr(uint32_t v)
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + N, 0xF, 0xF, false);    // row_shr:N, 0 shifted in
 }
 
-// one all-pairs step: partner = the lane N places away (inside the row)
-template <int N>
-__device__ __forceinline__ void pareto_step(uint32_t dist, uint32_t Lok, uint32_t t, bool& dom, uint32_t& rank)
+// The Pareto filter of a row: sort the row's 16 candidates by distance, then a candidate survives when it is longer
+// than everything nearer (an exclusive prefix maximum), and its place in the list is the number of survivors below it.
+//
+// Sort key.  Packed lists (dictionary <= 8 MiB): distance - 1 < 2^23 and L <= 273 < 2^9, so (distance - 1) << 9 | L is
+// one 32-bit word and a compare-exchange is v_min_u32 / v_max_u32; a lane without a candidate takes SORT_NONE, which
+// sorts behind every candidate and carries length 0.  Unpacked lists: the pair (distance - 1, L), ordered by the
+// distance alone, a lane without a candidate (0xFFFFFFFF, 0).
+// Ties.  Two lanes with the same distance name the same source position, and a position has ONE match length at x (lim
+// and the bytes are the same in every lane of the row), so wherever both are candidates their keys are identical:
+// which of them the network puts first cannot be seen in the result, and no lane number is needed as a tie-break.
+// (Where the lengths seem to differ -- L = 3 in the hash2 lane, whose minimum is 2, beside a lane whose minimum is 4 --
+// only one of the two is a candidate.)  The earlier all-pairs filter dropped the higher lane of such a pair "whatever
+// its length"; with equal lengths that is the rule "not longer than something sorted before it", which the prefix
+// maximum applies.
+//
+// Network: bitonic, written so that every layer sorts ascending (the first layer of a merge compares with the MIRROR
+// image inside the block, the others with lane ^ j), 10 layers.  Every partner is one DPP pattern inside the row
+// (quad_perm for lane ^ 1, ^ 2, ^ 3; row_half_mirror = lane ^ 7; row_mirror = lane ^ 15) but lane ^ 4, which is
+// row_shl:4 for banks 0 and 2 and row_shr:4 for banks 1 and 3.  No LDS, nothing crosses a row.
+constexpr uint32_t SORT_NONE = 0xFFFFFE00u;
+constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_XOR3 = 0x1B, DPP_XOR7 = 0x141, DPP_XOR15 = 0x140;   // quad_perm / mirrors
+constexpr int DPP_XOR4 = -1;
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t row_partner(uint32_t v)
 {
-    const uint32_t dj = row_ror<N>(dist), Lj = row_ror<N>(Lok), tj = row_ror<N>(t);
-    const bool before = Lj != 0 && (dj < dist || (dj == dist && tj < t));      // partner is a candidate and sorts before me
-    dom = dom || (before && (Lj >= Lok || dj == dist));
-    rank += before ? 1u : 0u;
+    if constexpr (CTRL == DPP_XOR4) {
+        const int up = __builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xF, 0x5, false);      // row_shl:4 -> lanes 0-3, 8-11
+        return (uint32_t)__builtin_amdgcn_update_dpp(up, (int)v, 0x114, 0xF, 0xA, false);   // row_shr:4 -> lanes 4-7, 12-15
+    } else {
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+    }
 }
-template <int N>
-__device__ __forceinline__ void count_step(uint32_t key, uint32_t t, uint32_t& idx)
+// one layer: `low` = this lane is the lower one of its pair and keeps the smaller key
+template <bool PACKED, int CTRL>
+__device__ __forceinline__ void sort_layer(uint32_t& key, uint32_t& len, bool low)
 {
-    const uint32_t kj = row_ror<N>(key), tj = row_ror<N>(t);
-    idx += (kj < key || (kj == key && tj < t)) ? 1u : 0u;
+    const uint32_t pk = row_partner<CTRL>(key);
+    if constexpr (PACKED) {
+        key = low ? min(key, pk) : max(key, pk);
+    } else {
+        const uint32_t pl = row_partner<CTRL>(len);
+        const bool take = (pk < key) != !low;          // (equal keys carry equal lengths: taking the partner's changes nothing)
+        key = take ? pk : key;
+        len = take ? pl : len;
+    }
+}
+template <bool PACKED>
+__device__ __forceinline__ void row_sort16(uint32_t& key, uint32_t& len, bool low1, bool low2, bool low4, bool low8)
+{
+    sort_layer<PACKED, DPP_XOR1>(key, len, low1);
+    sort_layer<PACKED, DPP_XOR3>(key, len, low2);  sort_layer<PACKED, DPP_XOR1>(key, len, low1);
+    sort_layer<PACKED, DPP_XOR7>(key, len, low4);  sort_layer<PACKED, DPP_XOR2>(key, len, low2);
+    sort_layer<PACKED, DPP_XOR1>(key, len, low1);
+    sort_layer<PACKED, DPP_XOR15>(key, len, low8); sort_layer<PACKED, DPP_XOR4>(key, len, low4);
+    sort_layer<PACKED, DPP_XOR2>(key, len, low2);  sort_layer<PACKED, DPP_XOR1>(key, len, low1);
 }
 
+// PACKED = the list format (a.list_packed): it only decides the sort key and the stores
+template <bool PACKED>
 __global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, uint16_t* __restrict__ mlen,
         uint32_t* __restrict__ mdist)
 {
@@ -158,8 +206,10 @@ __global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, ui
     const bool hash_lane = t >= 10;
     const uint32_t* __restrict__ hp = t == 10 ? sn.prev2 : t == 11 ? sn.prev24 : t == 12 ? sn.prev4 : t == 13 ? sn.prev8
             : t == 14 ? sn.prev16 : sn.prev32;
-    const uint32_t hstride = 1u;
     const uint32_t minlen = t == 10 ? 2u : 4u;
+    // the row sort: is this lane the lower one of a pair 1 / 2 / 4 / 8 lanes apart; the lanes below it inside the row
+    const bool low1 = !(t & 1), low2 = !(t & 2), low4 = !(t & 4), low8 = !(t & 8);
+    const uint32_t below = (1u << t) - 1;
     // masks for the prefix maximum inside a side (the right side must not look into the left one)
     const bool sh1 = t != 0 && t != 5, sh2 = (left && t >= 2) || (right && t >= 7), sh4 = (left && t >= 4) || (right && t >= 9);
 
@@ -225,12 +275,12 @@ __global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, ui
     geo_next(g2_bs, g2_be, xr0 + 2);
     uint32_t rk1 = sn.sa_rank[clampp(xr0 + 1)];
     uint32_t rk2 = sn.sa_rank[clampp(xr0 + 2)];
-    uint32_t hw1 = hash_lane ? hp[hstride * clampp(xr0 + 1)] : 0u;
+    uint32_t hw1 = hash_lane ? hp[clampp(xr0 + 1)] : 0u;
     uint32_t w1 = window(rk1, g1_bs, g1_be, xr0 + 1 < xend);
     uint32_t q0; bool v0;
     {
         const uint32_t rk0 = sn.sa_rank[clampp(xr0)];
-        const uint32_t hw0 = hash_lane ? hp[hstride * clampp(xr0)] : 0u;
+        const uint32_t hw0 = hash_lane ? hp[clampp(xr0)] : 0u;
         candidate(xr0, window(rk0, g_bs, g_be, xr0 < xend), hw0, q0, v0);
         if (!(xr0 < xend)) v0 = false;
     }
@@ -246,7 +296,7 @@ __global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, ui
         // stage 0: window of x + 2 (its rank arrived last iteration), rank of x + 3, hash word of x + 2
         const uint32_t w2 = window(rk2, g2_bs, g2_be, x + 2 < xend);
         const uint32_t rk3 = sn.sa_rank[clampp(x + 3)];
-        const uint32_t hw2 = hash_lane ? hp[hstride * clampp(x + 2)] : 0u;
+        const uint32_t hw2 = hash_lane ? hp[clampp(x + 2)] : 0u;
         // stage 1: candidates of x + 1 and their first 16 bytes
         uint32_t q1; bool v1;
         candidate(x + 1, w1, hw1, q1, v1);
@@ -257,7 +307,6 @@ __global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, ui
         // stage 2: position x
         uint32_t mval = 0;                                  // this position's 16-bit summary for the span plan (top lane)
         if (x < xend) {
-            const uint32_t q = q0;
             const bool valid = v0;
             const uint32_t avail = g_be - x;
             const uint32_t buf_avail = avail < MATCH_LEN_MAX ? avail : MATCH_LEN_MAX;
@@ -269,32 +318,35 @@ __global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, ui
             if (pf0) {
                 const uint32_t m = match16(A0, B0);
                 L = m < lim ? m : lim;
-                if (m == 16 && lim > 16) L = lane_cmplen16_from(in, q, x, 16, lim);
+                if (m == 16 && lim > 16) L = lane_cmplen16_from(in, q0, x, 16, lim);
             } else {
-                L = lane_cmplen16_from(in, q, x, 0, lim);
+                L = lane_cmplen16_from(in, q0, x, 0, lim);
             }
             const bool ok = lim != 0 && L >= minlen;
-            const uint32_t dist = x - q;                        // delta >= 1 on ok lanes
-            const uint32_t Lok = ok ? L : 0u;
-            // Pareto set inside the row: drop a candidate when another one sorts before it (closer, or the same
-            // position in a lower lane) and is at least as long; rank = candidates sorting before me
-            bool dom = false;
-            uint32_t rank = 0;
-            pareto_step<1>(dist, Lok, t, dom, rank); pareto_step<2>(dist, Lok, t, dom, rank); pareto_step<3>(dist, Lok, t, dom, rank);
-            pareto_step<4>(dist, Lok, t, dom, rank); pareto_step<5>(dist, Lok, t, dom, rank); pareto_step<6>(dist, Lok, t, dom, rank);
-            pareto_step<7>(dist, Lok, t, dom, rank); pareto_step<8>(dist, Lok, t, dom, rank); pareto_step<9>(dist, Lok, t, dom, rank);
-            pareto_step<10>(dist, Lok, t, dom, rank); pareto_step<11>(dist, Lok, t, dom, rank); pareto_step<12>(dist, Lok, t, dom, rank);
-            pareto_step<13>(dist, Lok, t, dom, rank); pareto_step<14>(dist, Lok, t, dom, rank); pareto_step<15>(dist, Lok, t, dom, rank);
-            const bool keep = ok && !dom;
+            // sort the row's candidates by distance (see row_sort16): from here on a lane holds the entry of its RANK, not
+            // the candidate it fetched
+            uint32_t skey, slen;
+            if constexpr (PACKED) {
+                skey = ok ? ((x - q0 - 1) << 9) | L : SORT_NONE;
+                slen = 0;
+            } else {
+                skey = ok ? x - q0 - 1 : SN_NONE;
+                slen = ok ? L : 0u;
+            }
+            row_sort16<PACKED>(skey, slen, low1, low2, low4, low8);
+            if constexpr (PACKED) slen = skey & 0x1FFu;
+            L = slen;                                           // 0 in the lanes behind the candidates
+            const uint32_t dist = (PACKED ? skey >> 9 : skey) + 1;
+            const uint32_t q = x - dist;
+            // Pareto set: a candidate stays when it is longer than every nearer one (the same position twice: equal
+            // keys, the second one goes)
+            uint32_t pm = L;
+            pm = max(pm, row_shr<1>(pm)); pm = max(pm, row_shr<2>(pm)); pm = max(pm, row_shr<4>(pm)); pm = max(pm, row_shr<8>(pm));
+            const bool keep = L > row_shr<1>(pm);
             // index among the kept entries in distance (= length) order, and their number
-            const uint32_t key = keep ? rank : 0xFFu;
-            uint32_t kidx = 0;
-            count_step<1>(key, t, kidx); count_step<2>(key, t, kidx); count_step<3>(key, t, kidx); count_step<4>(key, t, kidx);
-            count_step<5>(key, t, kidx); count_step<6>(key, t, kidx); count_step<7>(key, t, kidx); count_step<8>(key, t, kidx);
-            count_step<9>(key, t, kidx); count_step<10>(key, t, kidx); count_step<11>(key, t, kidx); count_step<12>(key, t, kidx);
-            count_step<13>(key, t, kidx); count_step<14>(key, t, kidx); count_step<15>(key, t, kidx);
-            const uint64_t kmask = __ballot(keep);
-            const uint32_t cnt = (uint32_t)__builtin_popcount((uint32_t)(kmask >> (lane & 48)) & 0xFFFFu);
+            const uint32_t kept = (uint32_t)(__ballot(keep) >> (lane & 48)) & 0xFFFFu;
+            const uint32_t cnt = (uint32_t)__builtin_popcount(kept);
+            const uint32_t kidx = (uint32_t)__builtin_popcount(kept & below);
             const bool top = keep && kidx + 1 == cnt, second = keep && kidx + 2 == cnt;
             uint32_t len_out = L;
             if (top && L == nice) len_out = lane_cmplen16_from(in, q, x, L, buf_avail);      // > nice_len extension
@@ -307,7 +359,7 @@ __global__ __launch_bounds__(64) void k_find_sn(xzamd_span_args a, SnArgs sn, ui
             const uint32_t drop = cnt > LIST_K ? cnt - LIST_K : 0;
             if (keep && kidx >= drop) {
                 const uint64_t o = rec_base + (kidx - drop);
-                if (a.list_packed) {
+                if constexpr (PACKED) {
                     mdist[o] = (len_out << 23) | (dist - 1);
                 } else {
                     mlen[o] = (uint16_t)len_out;
@@ -619,7 +671,9 @@ int xzk_find_matches(const xzamd_span_args* a, const uint32_t* sa, const uint32_
         sn.prev24 = prev24; sn.prev32 = prev32;
         sn.mode = (uint32_t)part;
         const uint32_t nblocks = (a->n + a->block_size - 1) / a->block_size;
-        hipLaunchKernelGGL(k_find_sn, dim3(part == 1 ? nblocks * SEED_RUNS : runs), dim3(64), 0, st, *a, sn, mlen, mdist);
+        const dim3 grid(part == 1 ? nblocks * SEED_RUNS : runs);
+        if (a->list_packed) hipLaunchKernelGGL(k_find_sn<true>, grid, dim3(64), 0, st, *a, sn, mlen, mdist);
+        else hipLaunchKernelGGL(k_find_sn<false>, grid, dim3(64), 0, st, *a, sn, mlen, mdist);
     } else {
         hipLaunchKernelGGL(k_find_exact, dim3(runs), dim3(64), 0, st, *a, mlen, mdist);
     }

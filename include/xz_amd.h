@@ -270,6 +270,17 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
 #define XZAMD_F_VERIFY 8u
 #define XZAMD_F_REPAIR 16u
 #define XZAMD_F_SINGLE 32u
+/* XZAMD_F_AUTO_DELTA: AUTOMATIC PER-BLOCK DELTA FILTER for the chain {LZMA2} (DESIGN.md 3.5 "Automatic delta").  For every
+ * Block the device counts byte histograms of a sample of the Block (4 KiB of every 64 KiB) as it is and after delta(d), d in
+ * {1, 2, 3, 4, 6, 8, 12, 16, 24, 32}, prices each with an integer order-0 entropy, and gives the Block the filter delta(d) with
+ * the lowest price when that is at least half a bit per byte below the unfiltered one; else the Block stays {LZMA2}.  The
+ * chain is written into each Block Header, so the Blocks of one Stream may differ: plain .xz, read by any decoder.  Blocks
+ * that go out stored carry no filter, as always.  Nothing but the flag is needed; the choice costs no host synchronisation.
+ * Allowed with XZAMD_F_BLOCKS_ONLY, _KEEP_RESUME and _VERIFY, every Check and every preset.  XZAMD_OPTIONS_ERROR with a filter
+ * already in front of LZMA2 (opt->bcj != 0), with XZAMD_F_SEGMENTS or XZAMD_F_SINGLE (a single Block has one chain), with
+ * XZAMD_F_REPAIR (the repair plans the headers of the Blocks it replaces from one chain for the whole Stream), and over a kernel
+ * layer without the entry points.  Without the flag no byte this library writes changes. */
+#define XZAMD_F_AUTO_DELTA 64u
 
 typedef struct {
 	uint64_t unpadded_size;      /* Index record field 1 (block_util.c:45-76) */
@@ -284,6 +295,14 @@ int xzamd_stream_encode_device(xzamd_ctx *ctx,
 		void *d_out, uint64_t out_cap, uint64_t *out_size,
 		xzamd_block_info *binfo, uint64_t binfo_cap, uint64_t *nblocks,
 		void *stream);
+
+/* The analysis of XZAMD_F_AUTO_DELTA on its own: dist_out[b] (host memory, cap entries) = the delta distance the rule picks
+ * for Block b of the in_size bytes at d_in cut into Blocks of block_size bytes, 0 = no filter; *nblocks = their number.
+ * XZAMD_BUF_ERROR when cap is too small (*nblocks is set), XZAMD_OPTIONS_ERROR for block_size 0 or >= 2 GiB or over a kernel
+ * layer without the entry points.  The histograms and choices stay fetchable (XZAMD_DEBUG_DELTA_HIST / _DIST) for inputs of
+ * one device batch. */
+int xzamd_auto_delta_device(xzamd_ctx *ctx, const void *d_in, uint64_t in_size, uint64_t block_size, uint32_t *dist_out,
+		uint64_t cap, uint64_t *nblocks, void *stream);
 
 /* Device .xz decoder (the reference's stream_decoder_mt.c / lzma2_decoder.c / lzma_decoder.c path, SURVEY.md
  * 8f.3): decode a single-Stream .xz file resident in device memory into d_out (trailing bytes, Stream Padding or a second
@@ -538,6 +557,8 @@ int xzamd_trace_read(xzamd_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *coun
 #define XZAMD_DEBUG_CARRY 16        /* the coder's walk, per encode-span slot: 0 = reset + properties, 1 = carried, 2 = flat start */
 #define XZAMD_DEBUG_CB_HDR 17       /* the coder's bounds walk, per encode-span slot: XZAMD_CB_* flags */
 #define XZAMD_DEBUG_CB_START 18     /* the coder's walk: the model at the span start, u16 per probability (padded to 64) */
+#define XZAMD_DEBUG_DELTA_HIST 19   /* XZAMD_F_AUTO_DELTA / xzamd_auto_delta_device, last batch: 11 x 256 x u32 per Block (candidates none, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32) */
+#define XZAMD_DEBUG_DELTA_DIST 20   /* ... the chosen distance per Block, u32 (0 = no filter) */
 int xzamd_debug_fetch(xzamd_ctx *ctx, int what, void *host_out, uint64_t bytes);
 
 /* Seeded synthetic corpora used by bench.py and the tests (host memory). */

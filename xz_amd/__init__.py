@@ -23,6 +23,9 @@ F_KEEP_RESUME = 4
 F_VERIFY = 8
 F_REPAIR = 16
 F_SINGLE = 32
+F_AUTO_DELTA = 64
+AUTO_DELTA_DISTANCES = (0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32)     # candidates of the automatic delta filter, 0 = none
+DEBUG_DELTA_HIST, DEBUG_DELTA_DIST = 19, 20
 VSTEPS = ("none", "grammar", "decode", "check", "compare")     # XZAMD_VSTEP_*
 NO_BLOCK = 0xFFFFFFFFFFFFFFFF
 BCJ_X86 = 4
@@ -187,6 +190,9 @@ def lib():
             l.xzamd_chains_repair_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(BlockInfo),
                                                      C.c_uint64, C.POINTER(LzmaOptions), C.c_int, C.c_void_p, C.c_uint64,
                                                      C.POINTER(C.c_uint64), C.POINTER(RepairReport), C.c_void_p]
+        if hasattr(l, "xzamd_auto_delta_device"):       # (an older library lacks the automatic delta filter)
+            l.xzamd_auto_delta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32),
+                                                  C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         l.xzamd_debug_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         l.xzamd_trace_enable.argtypes = [C.c_void_p, C.c_uint32]
         l.xzamd_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -330,7 +336,7 @@ class Encoder:
 
     def encode(self, data, opts=None, preset=6, block_size=0, check=CHECK_CRC64,
                span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0, repair=False,
-               single=False):
+               single=False, auto_delta=False):
         """Encode a CUDA uint8 tensor into an .xz Stream (CUDA uint8 tensor).
 
         Returns (out_tensor_view, block_infos). Runs on torch's current stream.
@@ -346,6 +352,8 @@ class Encoder:
         the block infos describe the segments (offset and length of each chunk chain inside the Stream, its CRC in
         unpadded_size).  Combinable with verify, keep_resume and repair, which then act on the segments' chains;
         Checks none / CRC32 / CRC64, no filter in front of LZMA2.
+        auto_delta: every Block gets the delta filter the device picks for it from byte histograms, or none
+        (XZAMD_F_AUTO_DELTA); for the chain {LZMA2} only, not with single or repair.
 
         Every XzAmdError raised here carries `code` (the XZAMD_* value; it used to be None for encode failures) and
         `stream` (what was written: empty unless the failure is a verification defect).
@@ -375,7 +383,7 @@ class Encoder:
         rc = lib().xzamd_stream_encode_device(
             self._ctx, C.c_void_p(data.data_ptr()), n, bs, C.byref(opts), check,
             (F_BLOCKS_ONLY if blocks_only else 0) | (F_VERIFY if verify else 0) | (F_KEEP_RESUME if keep_resume else 0)
-            | (F_REPAIR if repair else 0) | (F_SINGLE if single else 0) | flags,
+            | (F_REPAIR if repair else 0) | (F_SINGLE if single else 0) | (F_AUTO_DELTA if auto_delta else 0) | flags,
             C.c_void_p(out.data_ptr()), out.numel(),
             C.byref(out_size), binfo, max(nblocks, 1), C.byref(nb), C.c_void_p(stream))
         if rc != 0:
@@ -384,6 +392,34 @@ class Encoder:
             err.stream = out[: out_size.value]
             raise err
         return out[: out_size.value], list(binfo)[: nb.value]
+
+    def choose_delta(self, data, block_size):
+        """What encode(auto_delta=True) would pick for every Block of `block_size` bytes of `data` (CUDA uint8 tensor): the
+        list of delta distances, 0 = no filter (xzamd_auto_delta_device)."""
+        import torch
+        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
+        n = data.numel()
+        cap = max((n + block_size - 1) // block_size, 1) if block_size else 1
+        dist = (C.c_uint32 * cap)()
+        nb = C.c_uint64(0)
+        torch.cuda.current_stream(data.device).synchronize()
+        rc = lib().xzamd_auto_delta_device(self._ctx, C.c_void_p(data.data_ptr()), n, block_size, dist, cap, C.byref(nb), None)
+        if rc != 0:
+            raise XzAmdError(f"xzamd_auto_delta_device failed ({rc}): {lib().xzamd_last_error(self._ctx).decode()}", rc)
+        return list(dist)[: nb.value]
+
+    def delta_histograms(self, nblocks):
+        """The histograms and choices the last choose_delta / encode(auto_delta=True) of this context left for the
+        `nblocks` Blocks of its last batch: (uint32 array [nblocks, 11, 256] in the order of AUTO_DELTA_DISTANCES,
+        uint32 array [nblocks])."""
+        import numpy as np
+        hist = np.zeros((nblocks, len(AUTO_DELTA_DISTANCES), 256), dtype=np.uint32)
+        dist = np.zeros(nblocks, dtype=np.uint32)
+        for what, a in ((DEBUG_DELTA_HIST, hist), (DEBUG_DELTA_DIST, dist)):
+            rc = lib().xzamd_debug_fetch(self._ctx, what, C.c_void_p(a.ctypes.data), a.nbytes)
+            if rc != 0:
+                raise XzAmdError(f"xzamd_debug_fetch({what}) failed ({rc})", rc)
+        return hist, dist
 
     def verify_report(self):
         """The report of this context's last verification (`verify`, or an encode with verify=True) as a dict named like

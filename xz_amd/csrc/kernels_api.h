@@ -231,6 +231,15 @@ int xzk_x86_bcj(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_
 /* ARM64 BCJ (kind 0x0A) / delta (kind 3, dist 1..256) encoders, every Block filtered independently. */
 int xzk_prefilter(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t kind, uint32_t dist,
 		void *stream);
+/* Automatic per-Block delta filter (delta_rule.h).  The host units refer to the three weakly: over a kernel layer without
+ * them XZAMD_F_AUTO_DELTA is XZAMD_OPTIONS_ERROR.
+ * xzk_delta_stats: d_hist[nblocks][XZAMD_AD_NCAND][256] (uint32_t) = the byte histograms of every Block's sample set under
+ * the candidate distances (zeroed first).  xzk_delta_choose: d_dist[b] = the distance the rule picks for Block b, 0 = none.
+ * xzk_delta_blocks: d_out = d_in with Block b delta-filtered at d_dist[b], copied where that is 0. */
+int xzk_delta_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t *d_hist, void *stream);
+int xzk_delta_choose(const uint32_t *d_hist, uint32_t nblocks, uint32_t *d_dist, void *stream);
+int xzk_delta_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t *d_dist,
+		void *stream);
 /* SHA-256 of every Block (32 bytes each). */
 int xzk_sha256_blocks(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint8_t *d_out32, void *stream);
 /* Block checks: CRC64 (crc32 = 0) or CRC32 (crc32 = 1, zero-extended into d_block_crc). */

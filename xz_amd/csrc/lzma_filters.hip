@@ -5,6 +5,7 @@
 #include "kernels_api.h"
 #include "wave.h"
 #include "bcj_rules.h"
+#include "delta_rule.h"
 
 namespace {
 
@@ -310,6 +311,141 @@ __global__ __launch_bounds__(256) void k_delta(const uint8_t* __restrict__ in, u
 }
 
 // ------------------------------------------------------------------------------------------
+// Automatic per-Block delta filter (delta_rule.h, DESIGN.md 3.5 "Automatic delta"): byte histograms of the Block
+// under every candidate distance over a sample of the Block, an integer entropy cost per candidate, the choice, and the
+// delta encoder with the distance read per Block.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t AD_RUN = 8;            // sample windows per workgroup of k_delta_stats
+__device__ const uint8_t AD_LOG[256] = XZAMD_AD_LOG_TABLE;
+
+// One workgroup = AD_RUN consecutive sample windows of one Block; a thread = 16 bytes of a window and the 32 bytes in
+// front of them (three 16-byte loads where they lie inside the Block, single bytes at its two ends).  The 11 histograms
+// live in LDS and are added to the Block's in global memory once per workgroup.  hist must be zero on entry.
+__global__ __launch_bounds__(256) void k_delta_stats(const uint8_t* __restrict__ in, uint32_t n, uint32_t block_size,
+        uint32_t runs_per_block, uint32_t* __restrict__ hist)
+{
+    __shared__ uint32_t h[XZAMD_AD_HIST_WORDS];
+    const uint32_t blk = blockIdx.x / runs_per_block, run = blockIdx.x - blk * runs_per_block;
+    const uint64_t bs = (uint64_t)blk * block_size;
+    if (bs >= n) return;
+    const uint32_t blen = (uint32_t)min((uint64_t)block_size, (uint64_t)n - bs);
+    const uint8_t* __restrict__ b = in + bs;
+    for (uint32_t i = threadIdx.x; i < XZAMD_AD_HIST_WORDS; i += 256) h[i] = 0;
+    __syncthreads();
+    for (uint32_t w = run * AD_RUN; w < (run + 1) * AD_RUN; ++w) {
+        const uint64_t o64 = (uint64_t)w * XZAMD_AD_PERIOD + threadIdx.x * 16u;     // of this thread's 16 bytes in the Block
+        if (o64 >= blen) break;
+        const uint32_t o = (uint32_t)o64;
+        uint32_t x[12];                                   // bytes o - 32 .. o + 15 of the Block, zero outside of it
+        if (o >= 32 && o + 16 <= blen) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                uint4 v;
+                __builtin_memcpy(&v, b + o - 32 + 16 * q, 16);
+                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 12; ++q) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int64_t p = (int64_t)o - 32 + 4 * q + k;
+                    if (p >= 0 && p < (int64_t)blen) v |= (uint32_t)b[p] << (8 * k);
+                }
+                x[q] = v;
+            }
+        }
+        const uint32_t cnt = min(16u, blen - o);          // sampled bytes of this thread
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            if ((uint32_t)j < cnt) {
+                const uint32_t cur = (x[8 + j / 4] >> (8 * (j & 3))) & 255u;
+#pragma unroll
+                for (uint32_t k = 0; k < XZAMD_AD_NCAND; ++k) {
+                    const int p = 32 + j - (int)xzamd_ad_dist(k);      // k == 0: the byte itself, minus nothing
+                    const uint32_t prev = k == 0 ? 0u : (x[p / 4] >> (8 * (p & 3))) & 255u;
+                    atomicAdd(&h[k * 256 + ((cur - prev) & 255u)], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* __restrict__ g = hist + (uint64_t)blk * XZAMD_AD_HIST_WORDS;
+    for (uint32_t i = threadIdx.x; i < XZAMD_AD_HIST_WORDS; i += 256)
+        if (h[i]) atomicAdd(&g[i], h[i]);
+}
+
+// One wavefront per Block: S(k) = Ns * L(Ns) - sum_v hist[k][v] * L(hist[k][v]) for the 11 candidates, the rule,
+// dist[b] = the chosen distance (0: no filter).
+__global__ __launch_bounds__(64) void k_delta_choose(const uint32_t* __restrict__ hist, uint32_t nblocks,
+        uint32_t* __restrict__ dist)
+{
+    const uint32_t blk = blockIdx.x, lane = threadIdx.x;
+    if (blk >= nblocks) return;
+    const uint32_t* __restrict__ g = hist + (uint64_t)blk * XZAMD_AD_HIST_WORDS;
+    uint64_t S[XZAMD_AD_NCAND];
+    uint64_t Ns = 0;
+    for (uint32_t k = 0; k < XZAMD_AD_NCAND; ++k) {
+        uint64_t sum = 0, cnt = 0;
+        for (uint32_t v = lane; v < 256; v += 64) {
+            const uint32_t c = g[k * 256 + v];
+            sum += (uint64_t)c * xzamd_ad_log(c, AD_LOG);
+            cnt += c;
+        }
+        for (int s = 32; s > 0; s >>= 1) {
+            sum += __shfl_xor((unsigned long long)sum, s);
+            cnt += __shfl_xor((unsigned long long)cnt, s);
+        }
+        if (k == 0) Ns = cnt;
+        S[k] = Ns * xzamd_ad_log((uint32_t)Ns, AD_LOG) - sum;
+    }
+    if (lane == 0) dist[blk] = xzamd_ad_dist(xzamd_ad_rule(S, Ns));
+}
+
+// k_delta with the distance read per Block; a Block with distance 0 is copied, so that LZMA2 reads one buffer for the
+// whole batch.  A thread = 16 bytes of the batch: one 16-byte load of them and one of the bytes `dist` in front when
+// all of that lies inside one Block, single bytes at Block boundaries and at the end of the batch.
+__global__ __launch_bounds__(256) void k_delta_blocks(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
+        uint32_t block_size, const uint32_t* __restrict__ dist)
+{
+    const uint64_t nvec = ((uint64_t)n + 15) / 16;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nvec; t += stride) {
+        const uint32_t g = (uint32_t)(t * 16);
+        const uint32_t blk = g / block_size, off = g - blk * block_size;
+        if (g + 16 <= n && off + 16 <= block_size) {
+            const uint32_t d = dist[blk];
+            uint4 c;
+            __builtin_memcpy(&c, in + g, 16);
+            if (d != 0 && off >= d) {
+                uint4 p;
+                __builtin_memcpy(&p, in + g - d, 16);
+                // bytewise c - p: the borrow of every byte is kept out of its neighbour
+                const uint32_t cw[4] = { c.x, c.y, c.z, c.w }, pw[4] = { p.x, p.y, p.z, p.w };
+                uint32_t r[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    r[q] = ((cw[q] | 0x80808080u) - (pw[q] & 0x7F7F7F7Fu)) ^ ((cw[q] ^ ~pw[q]) & 0x80808080u);
+                c = make_uint4(r[0], r[1], r[2], r[3]);
+                __builtin_memcpy(out + g, &c, 16);
+            } else if (d != 0) {
+                for (uint32_t j = 0; j < 16; ++j)
+                    out[g + j] = (uint8_t)(in[g + j] - (off + j >= d ? in[g + j - d] : (uint8_t)0));
+            } else {
+                __builtin_memcpy(out + g, &c, 16);
+            }
+        } else {
+            const uint32_t e = min(n, g + 16);
+            for (uint32_t q = g; q < e; ++q) {
+                const uint32_t bq = q / block_size, oq = q - bq * block_size, d = dist[bq];
+                out[q] = (uint8_t)(in[q] - (d != 0 && oq >= d ? in[q - d] : (uint8_t)0));
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // SHA-256 Block check (check/sha256.c:120-189, FIPS 180-4): a serial hash per Block, so one THREAD per
 // Block (Blocks are the parallelism; the default Check, CRC64, stays the fast path).  32 bytes per Block.
 // ------------------------------------------------------------------------------------------
@@ -535,6 +671,38 @@ int xzk_prefilter(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t bloc
     } else {
         return (int)hipErrorInvalidValue;
     }
+    return (int)hipGetLastError();
+}
+
+int xzk_delta_stats(const uint8_t* d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t* d_hist, void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    if (nblocks == 0 || n == 0) return 0;
+    if (block_size == 0 || (uint64_t)nblocks * block_size < n) return (int)hipErrorInvalidValue;
+    int e = (int)hipMemsetAsync(d_hist, 0, (uint64_t)nblocks * XZAMD_AD_HIST_WORDS * 4, st);
+    if (e) return e;
+    const uint32_t wpb = (block_size + XZAMD_AD_PERIOD - 1) / XZAMD_AD_PERIOD;     // sample windows per full Block
+    const uint32_t rpb = (wpb + AD_RUN - 1) / AD_RUN;
+    const uint64_t grid = (uint64_t)rpb * nblocks;
+    if (grid > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_delta_stats, dim3((uint32_t)grid), dim3(256), 0, st, d_in, n, block_size, rpb, d_hist);
+    return (int)hipGetLastError();
+}
+
+int xzk_delta_choose(const uint32_t* d_hist, uint32_t nblocks, uint32_t* d_dist, void* stream_)
+{
+    if (nblocks == 0) return 0;
+    hipLaunchKernelGGL(k_delta_choose, dim3(nblocks), dim3(64), 0, (hipStream_t)stream_, d_hist, nblocks, d_dist);
+    return (int)hipGetLastError();
+}
+
+int xzk_delta_blocks(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t* d_dist,
+        void* stream_)
+{
+    if (n == 0) return 0;
+    if (block_size == 0 || (uint64_t)nblocks * block_size < n || n > 0xFFFFFFE0u) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_delta_blocks, dim3(grid_for(((uint64_t)n + 15) / 16, 256, 65536)), dim3(256), 0, (hipStream_t)stream_, d_in, d_out,
+            n, block_size, d_dist);
     return (int)hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/xz_amd.h"
 #include "kernels_api.h"
 #include "xzamd_internal.h"
+#include "delta_rule.h"
 
 #include <stdio.h>
 #include <pthread.h>
@@ -68,6 +69,8 @@ typedef struct {
 	uint32_t span;               /* span size of the fixed plan */
 	uint32_t spb, esb, cpb;      /* per Block: span slots, encode-span slots, estimate chunks */
 	uint32_t cbytes, hs_fixed;
+	uint32_t hs_delta;           /* XZAMD_F_AUTO_DELTA: header size of a Block that got a delta filter (hs_fixed: of one that got none) */
+	int auto_delta;
 	int segments;                  /* XZAMD_F_SEGMENTS: per Block only its chunk chain */
 	xzamd_mode m;
 	call_knobs k;
@@ -105,6 +108,7 @@ struct xzamd_ctx {
 	dbuf cb_bnd[2], cb_log[2], cb_hdr[2], cb_start[2], cb_carry[2]; /* carried model walk: [0] over iteration 1's records (front end), [1] the coder's (back end) */
 	dbuf sym_len[2], sym_dist[2], prior, enc_tab[2], enc_cnt[2];   /* two-phase mode ([2]: one set per pipeline parity) */
 	dbuf tok, chunks, h_chunks;                                    /* coder of the two-phase mode: tokens, chunk table */
+	dbuf dhist, ddist[2];                                          /* XZAMD_F_AUTO_DELTA: histograms of the batch, chosen distance per Block (per pipeline parity) */
 	dbuf resume_sr;                                                /* what the token walk of every encode span started from (resume table asked for) */
 	/* The resume table of the last encode with XZAMD_F_KEEP_RESUME / _VERIFY (kernels_api.h), kept until the next encode;
 	 * not a per-batch buffer: it lives for the call and beyond */
@@ -113,7 +117,7 @@ struct xzamd_ctx {
 	xzamd_verify_report report;                                    /* of the last verification */
 	xzamd_repair_report repair;                                    /* of the last repair */
 	/* pinned host buffers */
-	dbuf h_span_bytes, h_block_crc, h_segs, h_lits, h_span_tab, h_span_cnt[2], h_enc_tab[2], h_enc_cnt[2], h_err[2];
+	dbuf h_span_bytes, h_block_crc, h_segs, h_lits, h_span_tab, h_span_cnt[2], h_enc_tab[2], h_enc_cnt[2], h_err[2], h_ddist[2];
 	void *evp[2][EV_COUNT];
 	void *ev_total[2];
 	uint32_t trace_cap;
@@ -227,19 +231,19 @@ static void ctx_device_bufs(xzamd_ctx *c, dbuf **d, size_t *nd)
 {
 	dbuf *all[] = { &c->keys_a, &c->keys_b, &c->vals_a, &c->vals_b, &c->rank, &c->sorted_pos,
 		&c->prev2, &c->prev3, &c->prev4, &c->prev8, &c->prev16, &c->prev24, &c->prev32, &c->key64_a, &c->key64_b, &c->sa, &c->sa_rank, &c->sort_tmp,
-		&c->scratch, &c->litp, &c->mlen, &c->mdist, &c->bcj[0], &c->bcj[1], &c->bcjt, &c->est, &c->mtop, &c->order,
+		&c->scratch, &c->litp, &c->mlen, &c->mdist, &c->bcj[0], &c->bcj[1], &c->bcjt, &c->est, &c->mtop, &c->order, &c->dhist,
 		&c->sym_len[0], &c->sym_len[1], &c->sym_dist[0], &c->sym_dist[1], &c->tok, &c->cb_log[0], &c->cb_log[1],
 		/* small ones */
 		&c->chunks,
 		&c->span_bytes, &c->strip_crc, &c->block_crc, &c->segs, &c->lits, &c->trace, &c->errw, &c->errw2,
 		&c->totals, &c->span_tab[0], &c->span_tab[1], &c->span_cnt[0], &c->span_cnt[1], &c->prior, &c->enc_tab[0], &c->enc_tab[1], &c->enc_cnt[0], &c->enc_cnt[1],
 		&c->pinfo[0], &c->pinfo[1], &c->snap_sr, &c->part_tab, &c->cb_bnd[0], &c->cb_bnd[1], &c->cb_hdr[0], &c->cb_hdr[1], &c->cb_start[0], &c->cb_start[1],
-		&c->cb_carry[0], &c->cb_carry[1], &c->resume_sr };
+		&c->cb_carry[0], &c->cb_carry[1], &c->resume_sr, &c->ddist[0], &c->ddist[1] };
 	_Static_assert(sizeof(all) / sizeof(all[0]) <= CTX_NBUF_MAX, "ctx_device_bufs: raise CTX_NBUF_MAX");
 	*nd = sizeof(all) / sizeof(all[0]);
 	memcpy(d, all, sizeof(all));
 }
-#define CTX_NBIG 35      /* the first CTX_NBIG entries of ctx_device_bufs scale with the batch */
+#define CTX_NBIG 36      /* the first CTX_NBIG entries of ctx_device_bufs scale with the batch */
 
 void xzamd_ctx_destroy(xzamd_ctx *c)
 {
@@ -258,7 +262,7 @@ void xzamd_ctx_destroy(xzamd_ctx *c)
 		if (d[i]->p) xzk_free(d[i]->p);
 	if (c->resume_tab.p) xzk_free(c->resume_tab.p);
 	dbuf *h[] = { &c->h_span_bytes, &c->h_block_crc, &c->h_segs, &c->h_lits, &c->h_span_tab, &c->h_span_cnt[0], &c->h_span_cnt[1],
-		&c->h_enc_tab[0], &c->h_enc_tab[1], &c->h_enc_cnt[0], &c->h_enc_cnt[1], &c->h_err[0], &c->h_err[1], &c->h_chunks };
+		&c->h_enc_tab[0], &c->h_enc_tab[1], &c->h_enc_cnt[0], &c->h_enc_cnt[1], &c->h_err[0], &c->h_err[1], &c->h_chunks, &c->h_ddist[0], &c->h_ddist[1] };
 	for (size_t i = 0; i < sizeof(h) / sizeof(h[0]); ++i)
 		if (h[i]->p) xzk_host_free(h[i]->p);
 	for (int i = 0; i < 2 * EV_COUNT; ++i)
@@ -363,6 +367,12 @@ extern int xzamd_chains_encoded_(xzamd_ctx *c, void *d_out, uint64_t size, uint6
 extern int xzamd_single_encode_(xzamd_ctx *c, const void *d_in, uint64_t in_size, uint64_t block_size, const xzamd_lzma_options *opt,
 		int check, uint32_t flags, void *d_out, uint64_t out_cap, uint64_t *out_size, xzamd_block_info *binfo, uint64_t binfo_cap,
 		uint64_t *nsegments, void *stream) __attribute__((weak));
+/* ... and the kernels of the automatic delta filter (lzma_filters.hip): without them XZAMD_F_AUTO_DELTA is XZAMD_OPTIONS_ERROR */
+extern int xzk_delta_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t *d_hist, void *stream)
+		__attribute__((weak));
+extern int xzk_delta_choose(const uint32_t *d_hist, uint32_t nblocks, uint32_t *d_dist, void *stream) __attribute__((weak));
+extern int xzk_delta_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks,
+		const uint32_t *d_dist, void *stream) __attribute__((weak));
 xzamd_repair_report *xzamd_ctx_repair_report_(xzamd_ctx *c) { return &c->repair; }
 /* A repair re-encodes Blocks on the context of the call it repairs: the kept table leaves the context meanwhile (the
  * re-encode would free it), the stats of the repaired call come back afterwards */
@@ -411,7 +421,8 @@ int xzamd_debug_fetch(xzamd_ctx *c, int what, void *out, uint64_t bytes)
 			: what == XZAMD_DEBUG_ENC_TAB ? &c->enc_tab[c->last_par] : what == XZAMD_DEBUG_ENC_CNT ? &c->enc_cnt[c->last_par]
 			: what == XZAMD_DEBUG_PINFO ? &c->pinfo[c->last_par] : what == XZAMD_DEBUG_SNAP_SR ? &c->snap_sr
 			: what == XZAMD_DEBUG_PRIOR ? &c->prior : what == XZAMD_DEBUG_CARRY ? &c->cb_carry[1]
-			: what == XZAMD_DEBUG_CB_HDR ? &c->cb_hdr[1] : what == XZAMD_DEBUG_CB_START ? &c->cb_start[1] : NULL;
+			: what == XZAMD_DEBUG_CB_HDR ? &c->cb_hdr[1] : what == XZAMD_DEBUG_CB_START ? &c->cb_start[1]
+			: what == XZAMD_DEBUG_DELTA_HIST ? &c->dhist : what == XZAMD_DEBUG_DELTA_DIST ? &c->ddist[c->last_par] : NULL;
 	if (!b || !b->p || b->cap < bytes)
 		return XZAMD_PROG_ERROR;
 	xzk_set_device(c->device);
@@ -512,6 +523,16 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		return fail(c, XZAMD_PROG_ERROR, "check id out of range", 0);
 	/* (internal callers only: the three flags act on the chains of the segments, xzamd_chains.c) */
 	const int chains = (flags & XZAMD_F_CHAINS_) != 0;
+	if (flags & XZAMD_F_AUTO_DELTA) {
+		if (!xzk_delta_stats || !xzk_delta_choose || !xzk_delta_blocks)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: this build has no kernels for it", 0);
+		if (opt->bcj != 0)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: the chain already has a filter in front of LZMA2", 0);
+		if (flags & XZAMD_F_SEGMENTS)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: Blocks only -- the segments of one Block share its chain", 0);
+		if (flags & XZAMD_F_REPAIR)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: not with XZAMD_F_REPAIR (the repair plans Block Headers from one chain)", 0);
+	}
 	if (chains && (!(flags & XZAMD_F_SEGMENTS) || !xzamd_chains_encoded_))
 		return fail(c, XZAMD_OPTIONS_ERROR, "chains: this build has no unit for bare chunk chains", 0);
 	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_SEGMENTS) && !chains)
@@ -574,6 +595,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	 * the batch is capped at 80 % of what is free now plus what this context already holds. */
 	{
 		double per_byte = xzamd_work_bytes_per_byte_(opt);
+		if (flags & XZAMD_F_AUTO_DELTA) per_byte += xzamd_auto_delta_bytes_per_byte_(block_size);
 		/* the resume table (only when asked for): one record per encode-span slot, for the whole call */
 		if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && J->m.two)
 			per_byte += (double)(XZAMD_RESUME_BYTES(J->m.model_slots) + 32u) * (double)(block_size / XZAMD_ENC_MIN_LEN + 1) / (double)block_size;
@@ -599,6 +621,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	J->esb = two ? (uint32_t)(block_size / XZAMD_ENC_MIN_LEN + 1) : 0;      /* encode-span slots per Block */
 	J->cpb = (uint32_t)((block_size + XZAMD_EST_CHUNK - 1) / XZAMD_EST_CHUNK);
 	J->filtered = opt->bcj != 0;          /* any filter in front of LZMA2: the encoder reads a filtered copy */
+	J->auto_delta = (flags & XZAMD_F_AUTO_DELTA) != 0;     /* ... or the copy in which every Block has the filter chosen for it */
 	/* Two-stream pipeline (two-phase mode): the back end of batch i -- range coder, checks, sizes, gather -- runs on the
 	 * second stream while the front end of batch i + 1 -- match structures, plan, parse -- runs on the caller's: the coder
 	 * is a few thousand latency-bound wavefronts, the structure build is HBM-bound, they share the GPU well.  The
@@ -620,6 +643,12 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	J->bound = xzamd_block_buffer_bound(block_size);
 	J->binfo = binfo; J->binfo_cap = binfo_cap;
 	J->cbytes = cbytes; J->hs_fixed = xzamd_block_header_size_(J->bound, block_size, opt);
+	if (J->auto_delta) {
+		/* the header is per Block: one of two sizes (every delta distance takes the same three bytes of Filter Flags) */
+		xzamd_lzma_options view = *opt;
+		view.bcj = XZAMD_FILTER_DELTA(1);
+		J->hs_delta = xzamd_block_header_size_(J->bound, block_size, &view);
+	}
 	J->check = check;
 	J->dbyte = xzamd_dict_size_byte_(opt->dict_size);
 	J->st = st; J->stb = J->pipelined ? c->st2 : st;
@@ -802,7 +831,12 @@ static int batch_reserve(xzamd_ctx *c, const job_env *J, const batch_run *B)
 	NEED(lits, B->max_lits, 0);
 	NEED(h_segs, B->max_segs * sizeof(xzamd_copy_seg), 1);
 	NEED(h_lits, B->max_lits, 1);
-	if (J->filtered) NEED(bcj[par], n + 16, 0);
+	if (J->filtered || J->auto_delta) NEED(bcj[par], n + 16, 0);
+	if (J->auto_delta) {
+		NEED(dhist, 4ull * XZAMD_AD_HIST_WORDS * nb, 0);
+		NEED(ddist[par], 4 * nb, 0);
+		NEED(h_ddist[par], 4 * nb + 16, 1);
+	}
 	if (opt->bcj2) NEED(bcjt, n + 16, 0);
 #undef NEED
 	return r;
@@ -1011,6 +1045,15 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 	}
 	const uint64_t pad = (4 - (payload & 3)) & 3;
 	const uint64_t bstart = opos;
+	/* the Block's own chain (XZAMD_F_AUTO_DELTA): the job's options with the filter chosen for this Block */
+	xzamd_lzma_options bopt = *J->opt;
+	uint32_t hs_coded = J->hs_fixed;
+	if (J->auto_delta) {
+		const uint32_t d = ((const uint32_t *)c->h_ddist[par].p)[b];
+		if (d > XZAMD_AD_MAXDIST)
+			return fail(c, XZAMD_PROG_ERROR, "automatic delta: distance out of range", 0);
+		if (d != 0) { bopt.bcj = XZAMD_FILTER_DELTA(d); hs_coded = J->hs_delta; }
+	}
 	uint64_t unp;
 	uint8_t tail[48];
 	uint32_t tl = 0;
@@ -1052,7 +1095,7 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 		*opos_io = opos;
 		return XZAMD_OK;
 	}
-	if (J->hs_fixed + payload + pad + cbytes > J->bound) {
+	if (hs_coded + payload + pad + cbytes > J->bound) {
 		/* stream_encoder_mt.c:298,316-344 -> block_buffer_encoder.c:88-162 */
 		const uint64_t csz = usize + ((usize + 65535) / 65536) * 3 + 1;
 		const uint32_t hs = xzamd_block_header_size_(csz, usize, NULL);      /* stored Blocks drop the filters in front of LZMA2 */
@@ -1073,9 +1116,9 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 		++c->stats.blocks_stored;
 		*stored_out = 1;
 	} else {
-		if (opos + J->hs_fixed + payload + pad + cbytes > J->out_cap) return fail(c, XZAMD_BUF_ERROR, "output buffer too small", 0);
-		xzamd_block_header_put_(small, J->hs_fixed, payload, usize, J->dbyte, J->opt);
-		opos = plan_lit(pl, small, J->hs_fixed, opos);
+		if (opos + hs_coded + payload + pad + cbytes > J->out_cap) return fail(c, XZAMD_BUF_ERROR, "output buffer too small", 0);
+		xzamd_block_header_put_(small, hs_coded, payload, usize, J->dbyte, &bopt);
+		opos = plan_lit(pl, small, hs_coded, opos);
 		for (uint32_t s = 0; s < nsp; ++s) {
 			const uint64_t slot = b * opb + s, start = otab[2 * slot];
 			if (two) {
@@ -1087,7 +1130,7 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 		}
 		tail[tl++] = 0x00;
 		for (uint64_t i = 0; i < pad; ++i) tail[tl++] = 0;
-		unp = J->hs_fixed + payload + cbytes;
+		unp = hs_coded + payload + cbytes;
 	}
 	if (check == XZAMD_CHECK_CRC64) {
 		const uint64_t v = bcrc[b];
@@ -1264,6 +1307,18 @@ static int front_input(xzamd_ctx *c, const job_env *J, batch_run *B)
 			if (e) return fail(c, XZAMD_DEVICE_ERROR, "filter in front of LZMA2", e);
 			src = dst;
 		}
+		B->enc_in = X;
+	}
+	if (J->auto_delta) {
+		/* statistic, choice and filter stay on the device, in stream order in front of the structure build; the choices
+		 * travel to the host behind them and are there when the layout (which waits for this stream's tables) reads them */
+		uint8_t *const X = (uint8_t *)c->bcj[B->par].p;
+		uint32_t *const dist = (uint32_t *)c->ddist[B->par].p;
+		int e = xzk_delta_stats(in, n, bs, nb, (uint32_t *)c->dhist.p, st);
+		if (!e) e = xzk_delta_choose((const uint32_t *)c->dhist.p, nb, dist, st);
+		if (!e) e = xzk_delta_blocks(in, X, n, bs, nb, dist, st);
+		if (!e) e = xzk_d2h(c->h_ddist[B->par].p, dist, 4ull * nb, st);
+		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic delta filter", e);
 		B->enc_in = X;
 	}
 	return XZAMD_OK;
@@ -1483,6 +1538,8 @@ int xzamd_stream_encode_device(xzamd_ctx *c,
 {
 	if (c && (flags & XZAMD_F_CHAINS_))
 		return fail(c, XZAMD_OPTIONS_ERROR, "unknown flag", 0);
+	if (c && (flags & XZAMD_F_SINGLE) && (flags & XZAMD_F_AUTO_DELTA))
+		return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: Blocks only -- the single Block of XZAMD_F_SINGLE has one chain", 0);
 	if (c && (flags & XZAMD_F_SINGLE)) {
 		if (!xzamd_single_encode_)
 			return fail(c, XZAMD_OPTIONS_ERROR, "single: this build has no unit for bare chunk chains", 0);
@@ -1491,6 +1548,45 @@ int xzamd_stream_encode_device(xzamd_ctx *c,
 	}
 	return xzamd_encode_device_(c, d_in_, in_size, block_size, opt, check, flags, d_out_, out_cap, out_size, binfo, binfo_cap,
 			nblocks_out, stream, NULL);
+}
+
+/* The analysis of XZAMD_F_AUTO_DELTA on its own: statistic and choice of every Block, a device batch at a time */
+int xzamd_auto_delta_device(xzamd_ctx *c, const void *d_in_, uint64_t in_size, uint64_t block_size, uint32_t *dist_out, uint64_t cap,
+		uint64_t *nblocks_out, void *stream)
+{
+	if (!c || (!d_in_ && in_size) || !nblocks_out || (!dist_out && cap))
+		return XZAMD_PROG_ERROR;
+	c->err[0] = 0;
+	if (!xzk_delta_stats || !xzk_delta_choose)
+		return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: this build has no kernels for it", 0);
+	if (block_size == 0 || block_size >= (1ull << 31))
+		return fail(c, XZAMD_OPTIONS_ERROR, "block_size must be 1 .. 2 GiB - 1", 0);
+	const uint64_t total = (in_size + block_size - 1) / block_size;
+	*nblocks_out = total;
+	if (total > cap)
+		return fail(c, XZAMD_BUF_ERROR, "dist_out too small", 0);
+	if (c->pend.active)
+		(void)pend_complete(c);      /* (its result is the deferred call's) */
+	void *st = stream ? stream : c->own_stream;
+	int e = xzk_set_device(c->device);
+	if (e) return fail(c, XZAMD_DEVICE_ERROR, "hipSetDevice", e);
+	uint64_t max_blocks = ((1ull << 31) - 1) / block_size;
+	if (max_blocks > (1u << 20)) max_blocks = 1u << 20;      /* (11 KiB of histograms per Block) */
+	c->last_par = 0;
+	for (uint64_t b0 = 0; b0 < total; b0 += max_blocks) {
+		const uint64_t nb = total - b0 < max_blocks ? total - b0 : max_blocks;
+		const uint64_t off = b0 * block_size;
+		const uint64_t n = in_size - off < nb * block_size ? in_size - off : nb * block_size;
+		int r = dgrow(c, &c->dhist, 4ull * XZAMD_AD_HIST_WORDS * nb, 0);
+		if (!r) r = dgrow(c, &c->ddist[0], 4 * nb, 0);
+		if (r) return r;
+		e = xzk_delta_stats((const uint8_t *)d_in_ + off, (uint32_t)n, (uint32_t)block_size, (uint32_t)nb, (uint32_t *)c->dhist.p, st);
+		if (!e) e = xzk_delta_choose((const uint32_t *)c->dhist.p, (uint32_t)nb, (uint32_t *)c->ddist[0].p, st);
+		if (!e) e = xzk_d2h(dist_out + b0, c->ddist[0].p, 4ull * nb, st);
+		if (!e) e = xzk_sync(st);
+		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic delta analysis", e);
+	}
+	return XZAMD_OK;
 }
 
 /* xzamd_stream_encode_device, and -- with deferred != NULL, XZAMD_F_BLOCKS_ONLY and the two-phase encode -- its pipelined

@@ -4,6 +4,7 @@
  * code: no device call and no context.
  */
 #include "xzamd_internal.h"
+#include "delta_rule.h"
 
 #include <string.h>
 
@@ -148,4 +149,11 @@ double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt)
 	}
 	if (opt->bcj) per_byte += opt->bcj2 ? 3.0 : 2.0;
 	return per_byte;
+}
+
+/* What XZAMD_F_AUTO_DELTA adds to that figure: the filtered copy (one per pipeline parity, like a filter named by the
+ * caller) and the 11 histograms of every Block. */
+double xzamd_auto_delta_bytes_per_byte_(uint64_t block_size)
+{
+	return 2.0 + 4.0 * XZAMD_AD_HIST_WORDS / (double)(block_size ? block_size : 1);
 }

@@ -140,6 +140,7 @@ struct lzma_internal_s {
 	uint64_t segment_env;        /* XZAMD_SEGMENT_KIB << 10, 0 = lzma_mt_block_size of the chain */
 	int repair;                  /* XZAMD_REPAIR=1 (read at init): every job runs with XZAMD_F_REPAIR -- on its Blocks, or in single mode on
 	                              * the chains of its segments -- and is finished before the next one is launched */
+	int auto_delta;              /* XZAMD_AUTO_DELTA=1 (read at init) on the plain chain {LZMA2}: every job runs with XZAMD_F_AUTO_DELTA */
 };
 
 static void *a_alloc(const lzma_allocator *a, size_t n)
@@ -350,7 +351,8 @@ static lzma_ret job_launch(lzma_internal *in, devslot *d, job *j, int io, int *r
 	void *cs = xzamd_ctx_stream_(d->ctx);
 	if (!injected && !(xzk_h2d(b->d_in, j->stage, n, cs) || xzk_sync(cs)) && (vlog("uploaded", j), 1))
 		*rc_out = xzamd_encode_device_(d->ctx, b->d_in, n, in->block_size, &j->opt, in->check,
-				in->single ? (in->repair ? XZAMD_F_SEGMENTS | XZAMD_F_CHAINS_ | XZAMD_F_REPAIR : XZAMD_F_SEGMENTS) : in->repair ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_REPAIR : XZAMD_F_BLOCKS_ONLY,
+				in->single ? (in->repair ? XZAMD_F_SEGMENTS | XZAMD_F_CHAINS_ | XZAMD_F_REPAIR : XZAMD_F_SEGMENTS) : in->repair ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_REPAIR
+						: (in->auto_delta && j->opt.bcj == 0) ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_AUTO_DELTA : XZAMD_F_BLOCKS_ONLY,
 				b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
 				&j->nblocks, NULL, ((nd && *nd == '1') || in->repair) ? NULL : deferred);
 	return LZMA_OK;
@@ -686,6 +688,10 @@ static lzma_ret encoder_init(lzma_stream *strm, lzma_ret r, const xzamd_lzma_opt
 		const char *rp = getenv("XZAMD_REPAIR");
 		/* (single mode: the chains of the segments are what is verified and replaced -- with the unit that does it) */
 		in->repair = rp && *rp == '1' && (!single || xzamd_chains_encoded_ != NULL);
+		/* XZAMD_AUTO_DELTA=1: the per-Block delta filter for clients that ask for the plain chain; ignored where the mode does
+		 * not apply -- the single-Block encoder, repaired jobs, and (per job: lzma_filters_update) a chain with filters */
+		const char *ad = getenv("XZAMD_AUTO_DELTA");
+		in->auto_delta = ad && *ad == '1' && !single && !in->repair;
 	}
 	in->sequence = ISEQ_RUN;
 	in->sseq = SEQ_HEADER;

@@ -197,6 +197,9 @@ typedef struct {
 	float ms_iter1;              /* two-phase: the part of ms_parse spent in the partial iteration(s) and the carried walk over their records;
 	                                ms_parse - ms_iter1 = the full parse (k_parse_pieces, iteration 2): the dominant kernel */
 	float ms_verify;             /* XZAMD_F_VERIFY: the verification of the finished Stream (wall time, not part of ms_total) */
+	uint32_t batches_ahead;      /* batches whose filters and structure build were issued ahead, under the parse of the batch before
+	                                (XZAMD_BUILD_AHEAD).  Their ms_chains spans a build that shares the GPU with that parse: it grows
+	                                while ms_total shrinks.  (The field takes the place of padding: the layout is what it was.) */
 } xzamd_stats;
 /* Stats of the last xzamd_stream_encode_device call of the context.  Under the lzma_* front end consecutive jobs of a
  * worker are pipelined (the back end of a job's last batch finishes underneath the next job's front end): there the stage

@@ -55,7 +55,7 @@ class Stats(C.Structure):
                 ("ms_find", C.c_float), ("span_size", C.c_uint32), ("ms_find_overlapped", C.c_float),
                 ("span_cost_used", C.c_uint32), ("ms_plan", C.c_float), ("wave_slots", C.c_uint32),
                 ("enc_spans", C.c_uint64), ("ms_seed", C.c_float), ("ms_parse", C.c_float), ("ms_code", C.c_float), ("ms_iter1", C.c_float),
-                ("ms_verify", C.c_float)]
+                ("ms_verify", C.c_float), ("batches_ahead", C.c_uint32)]
 
 
 class VerifyReport(C.Structure):

@@ -31,7 +31,9 @@ typedef struct {
 } dbuf;
 
 /* stage events of one batch (one set per parity of the two-stream pipeline) */
-enum { EV_START, EV_CHAINS, EV_FIND, EV_PLAN0, EV_PLAN1, EV_SEED, EV_ITER1, EV_PARSE, EV_FRONT, EV_BACK0, EV_CODE, EV_CRC, EV_ASM, EV_COUNT };
+enum { EV_START, EV_CHAINS, EV_FIND, EV_PLAN0, EV_PLAN1, EV_SEED, EV_PART, EV_ITER1, EV_PARSE, EV_FRONT, EV_BACK0, EV_CODE, EV_CRC, EV_ASM, EV_COUNT };
+/* (EV_PART: behind the last partial-iteration parse launch, in front of its snapshot walks; recorded only as a start point
+ * of the build ahead, no stage of the stats or of the progress) */
 
 /* One batch of Blocks: its geometry, and what its front end (match structures, plan, parse -- the caller's stream) hands
  * to its back end (range coder of the two-phase mode, Block checks, sizes, layout, gather -- the second stream when the
@@ -46,14 +48,20 @@ typedef struct {
 	uint64_t sort_bytes;         /* scratch of the sorts of the structure build */
 	int par;                     /* which set of the double-buffered tables / events this batch uses */
 	int sha_early;               /* its SHA-256 runs on the second stream from the batch's start */
+	int ahead;                   /* its filters and structure build were issued ahead, on the side stream, under the batch before */
 	const uint8_t *enc_in;       /* what LZMA2 reads (the filtered copy when a filter runs in front of it) */
 	uint64_t max_segs, max_lits;
 } batch_run;
+
+/* start points of the build ahead: behind the plan, the last partial parse launch, the partial iterations of the batch before */
+enum { AHEAD_PLAN = 1, AHEAD_PART, AHEAD_ITER1 };
+#define AHEAD_DEFAULT AHEAD_PLAN      /* measured best: profiles/build_ahead_ab.txt */
 
 /* knobs of the batch encode, read from the environment once per call */
 typedef struct {
 	int no_overlap;              /* XZAMD_NO_OVERLAP: one stream, no pipelining, no early seeds */
 	int back_beside_build;       /* XZAMD_BACK_BESIDE_BUILD: every back end right behind its own front end */
+	int build_ahead;             /* XZAMD_BUILD_AHEAD: where the next batch's structure build starts (AHEAD_*; 0: serial) */
 	int timing;                  /* XZAMD_TIMING: print what the kernels timed */
 	uint32_t tok_limit, log_cap; /* XZAMD_TEST_TOK_PER_BYTE, XZAMD_TEST_LOG_CAP (0: the built-in figures) */
 } call_knobs;
@@ -75,11 +83,14 @@ typedef struct {
 	xzamd_mode m;
 	call_knobs k;
 	int check, whole, filtered, pipelined, defer, seeds_early;
+	int ahead;                   /* != 0 (AHEAD_*): the filters and the structure build of batch i + 1 are issued on the side stream
+	                                behind that event of batch i (pipelined two-phase calls on the list-finder path) */
 	int resume, verify;          /* XZAMD_F_KEEP_RESUME / _VERIFY on a two-phase encode: resume records are exported; verify the Stream */
 	int repair;                  /* XZAMD_F_REPAIR: the verification is the per-Block one, rejected Blocks are replaced */
 	uint32_t rec_done;           /* resume records of the batches that are through their back end */
 	uint8_t dbyte;
 	void *st, *stb;              /* front-end stream (the caller's), back-end stream (the second one when pipelined) */
+	void *sta;                   /* side stream of the build ahead */
 	uint64_t *rec_unp, *rec_unc;
 	xzamd_block_info *binfo;
 	uint64_t opos;
@@ -90,7 +101,9 @@ struct xzamd_ctx {
 	void *own_stream;
 	void *st2;                   /* back-end stream: range coder, checks and gather of batch i run here while the front end
 	                                (match structures, plan, parse) of batch i + 1 runs on the caller's stream */
-	void *st3;                   /* the seed pieces of a batch run here, underneath the rest of its match finder */
+	void *st3;                   /* the seed pieces of a batch run here, underneath the rest of its match finder; and, in front of them,
+	                                the filters and the structure build that are issued ahead of their batch */
+	void *st4;                   /* measurement variants (XZAMD_BUILD_AHEAD_STREAM=own|low): a stream of its own for the build ahead */
 	void *ev_seed[2][3];            /* seed lists ready (caller's stream), seeds begin / done (st3) */
 	void *ev_sha;                /* SHA-256 of the batch (second stream) done */
 	uint64_t batch_bytes;
@@ -196,6 +209,14 @@ int xzamd_ctx_create(xzamd_ctx **out, int device)
 	if ((getenv("XZAMD_ST2_LOW") ? xzk_stream_create_low(&c->st2) : xzk_stream_create(&c->st2))) { c->st2 = NULL; xzamd_ctx_destroy(c); return XZAMD_DEVICE_ERROR; }
 	if (xzk_event_create(&c->ev_sha)) { c->ev_sha = NULL; xzamd_ctx_destroy(c); return XZAMD_DEVICE_ERROR; }
 	if (xzk_stream_create(&c->st3)) { c->st3 = NULL; xzamd_ctx_destroy(c); return XZAMD_DEVICE_ERROR; }
+	{
+		/* (measurement knob: the build ahead on a fourth stream, at normal or at the device's lowest priority) */
+		const char *sv = getenv("XZAMD_BUILD_AHEAD_STREAM");
+		const int low = sv && !strcmp(sv, "low");
+		if ((low || (sv && !strcmp(sv, "own"))) && (low ? xzk_stream_create_low(&c->st4) : xzk_stream_create(&c->st4))) {
+			c->st4 = NULL; xzamd_ctx_destroy(c); return XZAMD_DEVICE_ERROR;
+		}
+	}
 	for (int i = 0; i < 6; ++i)
 		if (xzk_event_create(&c->ev_seed[i / 3][i % 3])) { c->ev_seed[i / 3][i % 3] = NULL; xzamd_ctx_destroy(c); return XZAMD_DEVICE_ERROR; }
 	for (int i = 0; i < 2 * EV_COUNT; ++i)
@@ -272,6 +293,7 @@ void xzamd_ctx_destroy(xzamd_ctx *c)
 	if (c->ev_sha) xzk_event_destroy(c->ev_sha);
 	for (int i = 0; i < 6; ++i)
 		if (c->ev_seed[i / 3][i % 3]) xzk_event_destroy(c->ev_seed[i / 3][i % 3]);
+	if (c->st4) xzk_stream_destroy(c->st4);
 	if (c->st3) xzk_stream_destroy(c->st3);
 	if (c->st2) xzk_stream_destroy(c->st2);
 	if (c->own_stream) xzk_stream_destroy(c->own_stream);
@@ -501,6 +523,12 @@ static void knobs_read(call_knobs *k)
 	k->no_overlap = getenv("XZAMD_NO_OVERLAP") != NULL;
 	k->back_beside_build = getenv("XZAMD_BACK_BESIDE_BUILD") != NULL;
 	k->timing = getenv("XZAMD_TIMING") != NULL;
+	{
+		/* XZAMD_BUILD_AHEAD = 0 | plan | part | iter1: the event of batch i behind which the build of batch i + 1 starts */
+		const char *ba = getenv("XZAMD_BUILD_AHEAD");
+		k->build_ahead = !ba || !*ba ? AHEAD_DEFAULT : !strcmp(ba, "plan") ? AHEAD_PLAN : !strcmp(ba, "part") ? AHEAD_PART
+				: !strcmp(ba, "iter1") ? AHEAD_ITER1 : !strcmp(ba, "0") ? 0 : AHEAD_DEFAULT;
+	}
 	/* test knobs: a smaller token budget per input byte, fewer logged bits per span and probability (never more: the
 	 * buffers are what they are) */
 	k->tok_limit = knob_below(getenv("XZAMD_TEST_TOK_PER_BYTE"), XZAMD_TOK_PER_BYTE);
@@ -637,6 +665,11 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	/* two-phase: the lists of the seed regions first, so that the seed pieces (one wavefront per Block, latency
 	 * bound) can be parsed on a third stream underneath the rest of the finder (HBM bound) */
 	J->seeds_early = overlap_ok && block_size >= XZAMD_SEED_LEN + 1024;
+	/* Build ahead: on the list-finder path the structure is read by the finder only, so the build of batch i + 1 can run
+	 * under the parse of batch i.  The single-phase kernels read it while they code (never pipelined); a deferred batch is
+	 * carried into a call whose input is not known yet, so nothing is built ahead across calls. */
+	J->ahead = J->pipelined && opt->gpu_parser ? J->k.build_ahead : 0;
+	J->sta = c->st4 ? c->st4 : c->st3;
 
 	J->opt = opt; J->d_in = d_in; J->d_out = d_out; J->in_size = in_size; J->block_size = block_size; J->out_cap = out_cap;
 	J->total_blocks = total_blocks; J->max_blocks = max_blocks;
@@ -755,8 +788,9 @@ static int batch_geometry(xzamd_ctx *c, const job_env *J, uint64_t b0, batch_run
 }
 
 /* Every buffer of the batch at the size the batch needs.  Returns the first failure of dgrow: XZAMD_MEM_ERROR when the
- * device (or the pinned host memory) does not have it -- the batch loop then tries a smaller batch. */
-static int batch_reserve(xzamd_ctx *c, const job_env *J, const batch_run *B)
+ * device (or the pinned host memory) does not have it -- the batch loop then tries a smaller batch.  With `probe` it only
+ * asks whether a buffer would have to grow: a batch is issued ahead only into buffers that are already there. */
+static int batch_reserve(xzamd_ctx *c, const job_env *J, const batch_run *B, int probe)
 {
 	const xzamd_lzma_options *opt = J->opt;
 	const int two = J->m.two, par = B->par;
@@ -765,7 +799,8 @@ static int batch_reserve(xzamd_ctx *c, const job_env *J, const batch_run *B)
 	const uint64_t spb_crc = (J->block_size + CRC_STRIP - 1) / CRC_STRIP;
 	int r = 0;
 	/* (nothing more is asked for once one request has failed) */
-#define NEED(buf, bytes, host) (r = r ? r : dgrow(c, &c->buf, (bytes), host))
+	/* probe: nothing is allocated or freed; the answer is whether every buffer already has its size (0) or not (1) */
+#define NEED(buf, bytes, host) (r = r ? r : probe ? c->buf.cap < (uint64_t)(bytes) : dgrow(c, &c->buf, (bytes), host))
 	NEED(keys_a, 4 * n, 0); NEED(keys_b, 4 * n, 0);
 	NEED(vals_a, 4 * n, 0); NEED(vals_b, 4 * n, 0);
 	NEED(prev2, 4 * n, 0); NEED(prev3, 4 * n, 0);
@@ -1165,6 +1200,8 @@ static void back_stats(xzamd_ctx *c, const job_env *J, const batch_run *B)
 	const uint32_t *hcnt = (const uint32_t *)c->h_span_cnt[par].p;
 	float ms;
 	void **ev = c->evp[par];
+	/* (a batch that was issued ahead has EV_START and EV_CHAINS on the side stream: its build shares the GPU with the parse of
+	 * the batch before, so ms_chains grows with the knob while ms_total shrinks) */
 	if (!xzk_event_elapsed_ms(ev[EV_START], ev[EV_CHAINS], &ms)) c->stats.ms_chains += ms;
 	if (!xzk_event_elapsed_ms(ev[EV_CHAINS], ev[EV_FRONT], &ms)) c->stats.ms_encode += ms;
 	if (J->opt->gpu_parser && !xzk_event_elapsed_ms(ev[EV_CHAINS], ev[EV_FIND], &ms)) c->stats.ms_find += ms;
@@ -1188,6 +1225,7 @@ static void back_stats(xzamd_ctx *c, const job_env *J, const batch_run *B)
 		c->stats.span_cost_used = tgt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)tgt;
 	}
 	c->stats.batches += 1;
+	c->stats.batches_ahead += B->ahead != 0;
 	c->stats.encode_launches += 1;
 }
 
@@ -1277,11 +1315,10 @@ int xzamd_encode_finish_(xzamd_ctx *c, uint64_t *out_size)
 
 /* 0. What LZMA2 reads: the input, or -- with filters in front of LZMA2 -- the filtered copy (the Check and stored Blocks
  * read the original).  Also the batch's start event and, where it can run underneath everything else, its SHA-256. */
-static int front_input(xzamd_ctx *c, const job_env *J, batch_run *B)
+static int front_input(xzamd_ctx *c, const job_env *J, batch_run *B, void *st)
 {
 	const uint8_t *in = J->d_in + B->in_off;
 	const uint32_t n = B->n, bs = (uint32_t)J->block_size, nb = (uint32_t)B->nb;
-	void *st = J->st;
 	B->enc_in = in;
 	xzk_event_record(c->evp[B->par][EV_START], st);
 	if (J->check == XZAMD_CHECK_SHA256 && !J->pipelined) {
@@ -1324,26 +1361,71 @@ static int front_input(xzamd_ctx *c, const job_env *J, batch_run *B)
 	return XZAMD_OK;
 }
 
-/* 1. Match-finder structure.  The back end of the previous batch, when it has been left to this batch, starts behind it. */
-static int front_build(xzamd_ctx *c, const job_env *J, const batch_run *B, back_args *prev_back)
+/* 1. Match-finder structure, on the stream `st` (the caller's, or the side stream of a build ahead). */
+static int build_launch(xzamd_ctx *c, const job_env *J, const batch_run *B, void *st)
 {
 	const xzamd_lzma_options *opt = J->opt;
-	void **ev = c->evp[B->par];
 #define SA(buf) (opt->gpu_sa_window ? c->buf.p : NULL)     /* the suffix-neighbourhood finder's arrays */
 	int e = xzk_build_chains(B->enc_in, B->n, (uint32_t)J->block_size, (uint32_t)B->nb, J->hb, J->hmask, J->hbits, opt->gpu_sa_depth,
 			(uint32_t *)c->keys_a.p, (uint32_t *)c->keys_b.p, (uint32_t *)c->vals_a.p,
 			(uint32_t *)c->vals_b.p, c->sort_tmp.p, B->sort_bytes,
 			(uint32_t *)c->rank.p, (uint32_t *)c->sorted_pos.p, (uint32_t *)c->prev2.p, (uint32_t *)c->prev3.p,
 			(uint32_t *)SA(prev4), (uint64_t *)SA(prev8), (uint64_t *)SA(prev16), (uint64_t *)SA(key64_a), (uint64_t *)SA(key64_b),
-			(uint32_t *)SA(sa), (uint32_t *)SA(sa_rank), (uint32_t *)SA(prev24), (uint32_t *)SA(prev32), J->st);
+			(uint32_t *)SA(sa), (uint32_t *)SA(sa_rank), (uint32_t *)SA(prev24), (uint32_t *)SA(prev32), st);
 #undef SA
 	if (e) return fail(c, XZAMD_DEVICE_ERROR, "build_chains", e);
-	xzk_event_record(ev[EV_CHAINS], J->st);
+	xzk_event_record(c->evp[B->par][EV_CHAINS], st);
+	return XZAMD_OK;
+}
+
+/* The structure of the batch is built -- here, or ahead of time on the side stream, in which case the caller's stream only
+ * waits for it.  The back end of the previous batch, when it has been left to this batch, starts behind it. */
+static int front_build(xzamd_ctx *c, const job_env *J, const batch_run *B, back_args *prev_back)
+{
+	void **ev = c->evp[B->par];
+	int e = 0;
+	if (B->ahead) {
+		e = xzk_stream_wait_event(J->st, ev[EV_CHAINS]);
+		if (e) return fail(c, XZAMD_DEVICE_ERROR, "stream wait", e);
+	} else {
+		int rc = build_launch(c, J, B, J->st);
+		if (rc != XZAMD_OK) return rc;
+	}
 	if (!prev_back->valid)
 		return XZAMD_OK;
 	e = J->stb != J->st ? xzk_stream_wait_event(J->stb, ev[EV_CHAINS]) : 0;
 	if (e) return fail(c, XZAMD_DEVICE_ERROR, "stream wait", e);
 	return back_enqueue(c, J, prev_back);
+}
+
+/* Build ahead: once the front end of `cur` is enqueued and the batch before it is finished, the filters and
+ * the structure build of the batch behind `cur` go on the side stream, behind the start event of `cur` the call has chosen:
+ * they fill the snapshot walks and then run beneath the FULL parse.  Everything they write is dead by then -- the structure
+ * and the sorts' scratch since the finder and the plan's sort of `cur`, the filtered copy and the delta choices of this
+ * parity since the back end of the batch before `cur`, which the host has waited for (audit: DESIGN.md section 2).  Only into
+ * buffers that are there: a batch that would grow one is left to the loop, which runs it serially (next->ahead stays 0).
+ * The host waits inside the build for the side stream alone (the count of every doubling round). */
+static int ahead_issue(xzamd_ctx *c, const job_env *J, const batch_run *cur, batch_run *next)
+{
+	memset(next, 0, sizeof(*next));
+	const uint64_t b0 = cur->b0 + cur->nb;
+	if (!J->ahead || b0 >= J->total_blocks)
+		return XZAMD_OK;
+	batch_run N;
+	int rc = batch_geometry(c, J, b0, &N);
+	if (rc != XZAMD_OK) return rc;
+	N.par = (int)(c->par_seq & 1);
+	if (batch_reserve(c, J, &N, 1))
+		return XZAMD_OK;
+	void **evc = c->evp[cur->par];
+	int e = xzk_stream_wait_event(J->sta, evc[J->ahead == AHEAD_PLAN ? EV_PLAN1 : J->ahead == AHEAD_PART ? EV_PART : EV_ITER1]);
+	if (e) return fail(c, XZAMD_DEVICE_ERROR, "stream wait", e);
+	++c->par_seq;
+	N.ahead = 1;
+	*next = N;                       /* (from here on the side stream holds work of this batch: error paths drain it) */
+	rc = front_input(c, J, next, J->sta);
+	if (rc == XZAMD_OK) rc = build_launch(c, J, next, J->sta);
+	return rc;
 }
 
 /* the batch match finder: part 0 = every position, 1 = the seed regions, 2 = the rest */
@@ -1450,6 +1532,7 @@ static int front_parse(xzamd_ctx *c, const job_env *J, const batch_run *B, xzamd
 			a->iter = XZAMD_ITER_PARTIAL | (it ? XZAMD_ITER_SNAP : 0u);
 			if (it) e = xzk_memset(counter, 0, 4, st);
 			if (!e) e = xzk_parse_pieces(a, nb, 1, c->span_waves, counter, st);
+			if (J->ahead == AHEAD_PART && it + 1 == npart) xzk_event_record(ev[EV_PART], st);
 			if (!e) e = xzk_model_snapshots(a, nb, st);
 		}
 		xzk_event_record(ev[EV_ITER1], st);
@@ -1521,6 +1604,8 @@ static int batches_drain_release(xzamd_ctx *c, job_env *J, back_args *BA, batch_
 	}
 	xzk_sync(J->st);
 	xzk_sync(c->st2);
+	xzk_sync(J->sta);                /* (a build ahead is never in flight here -- it is issued only into buffers that are there, and
+	                                  * its batch then skips the reservation -- but the buffers go next: nothing may be running) */
 	dbuf *d[CTX_NBUF_MAX];
 	size_t nd = 0;
 	ctx_device_bufs(c, d, &nd);
@@ -1622,26 +1707,34 @@ int xzamd_encode_device_(xzamd_ctx *c,
 	memset(&prev, 0, sizeof(prev));
 	back_args BA;                    /* valid: the back end of `prev` has not been enqueued yet */
 	memset(&BA, 0, sizeof(BA));
+	batch_run next;                  /* ahead: the batch behind the current one, its build already on the side stream */
+	memset(&next, 0, sizeof(next));
 	progress_set(c, 0, 0, 0);
 	xzk_event_record(c->ev_total[0], J.st);
 	for (uint64_t b0 = 0; b0 < J.total_blocks && rc == XZAMD_OK; ) {
 		batch_run cur;
 		xzamd_span_args a;
-		rc = batch_geometry(c, &J, b0, &cur);
-		if (rc != XZAMD_OK) break;
-		cur.par = J.pipelined ? (int)(c->par_seq++ & 1) : 0;
-		rc = batch_reserve(c, &J, &cur);
-		if (rc == XZAMD_MEM_ERROR && cur.nb > 1) {
-			/* out of device memory: this batch again with half the Blocks */
-			J.max_blocks = (cur.nb + 1) / 2;
-			rc = batches_drain_release(c, &J, &BA, &prev);
-			continue;
+		if (next.ahead) {
+			/* its geometry, buffers, filters and build were dealt with under the batch before */
+			cur = next;
+			next.ahead = 0;
+		} else {
+			rc = batch_geometry(c, &J, b0, &cur);
+			if (rc != XZAMD_OK) break;
+			cur.par = J.pipelined ? (int)(c->par_seq++ & 1) : 0;
+			rc = batch_reserve(c, &J, &cur, 0);
+			if (rc == XZAMD_MEM_ERROR && cur.nb > 1) {
+				/* out of device memory: this batch again with half the Blocks */
+				J.max_blocks = (cur.nb + 1) / 2;
+				rc = batches_drain_release(c, &J, &BA, &prev);
+				continue;
+			}
+			if (rc != XZAMD_OK) break;
 		}
-		if (rc != XZAMD_OK) break;
 		cur.active = 1;
 		c->last_par = cur.par;
 
-		rc = front_input(c, &J, &cur);
+		if (!cur.ahead) rc = front_input(c, &J, &cur, J.st);
 		if (rc == XZAMD_OK) rc = front_build(c, &J, &cur, &BA);
 		if (rc == XZAMD_OK) {
 			span_args_init(c, &J, &cur, &a);
@@ -1650,6 +1743,10 @@ int xzamd_encode_device_(xzamd_ctx *c,
 		if (rc == XZAMD_OK) rc = front_plan(c, &J, &cur, &a);
 		if (rc == XZAMD_OK) rc = front_parse(c, &J, &cur, &a);
 		if (rc == XZAMD_OK) rc = back_stage(c, &J, &cur, &a, &BA, &prev);
+		/* Order on the host: the batch before `cur` has just been finished (back_stage: layout and gather, no later than
+		 * without the build ahead), and the finder of `cur` is still running, so the build of the next batch is enqueued
+		 * before its start event fires.  The host then waits inside that build, where the serial order waited too. */
+		if (rc == XZAMD_OK) rc = ahead_issue(c, &J, &cur, &next);
 		b0 += cur.nb;
 	}
 	if (rc == XZAMD_OK && c->pend.active)
@@ -1670,6 +1767,7 @@ int xzamd_encode_device_(xzamd_ctx *c,
 		pend_complete(c);            /* this call failed before it got there: the carried batch still gets finished */
 	xzk_sync(J.st);
 	xzk_sync(c->st3);
+	if (J.sta != c->st3) xzk_sync(J.sta);     /* (either one: also a build ahead that an error left behind) */
 	if (!(deferred && *deferred))
 		xzk_sync(c->st2);          /* a back end abandoned by an error path */
 	if (rc == XZAMD_OK && J.whole)

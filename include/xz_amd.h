@@ -284,6 +284,19 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
  * XZAMD_F_REPAIR (the repair plans the headers of the Blocks it replaces from one chain for the whole Stream), and over a kernel
  * layer without the entry points.  Without the flag no byte this library writes changes. */
 #define XZAMD_F_AUTO_DELTA 64u
+/* XZAMD_F_AUTO_BCJ: AUTOMATIC PER-BLOCK BCJ FILTER for the chain {LZMA2} (DESIGN.md 3.5 "Automatic BCJ").  For every Block the
+ * device finds the call sites of two candidates over the whole Block -- x86 (E8 / E9 whose operand's top byte is 00 / FF) and
+ * ARM64 (BL at a 4-byte offset of the Block) -- counts 4096-bucket hashed histograms of their operands as stored and as the
+ * filter would store them (made absolute), prices both with the integer order-0 entropy of the automatic delta, and gives the
+ * Block the filter when it has at least 256 sites, one per 2 KiB or denser, and the absolute operands are at least half a bit
+ * per site cheaper; of two candidates that qualify the one that saves more, x86 on a tie; else the Block stays {LZMA2}.  The
+ * Block is then filtered exactly as the fixed chain {x86, LZMA2} / {ARM64, LZMA2} filters it, and the chain is written into
+ * its Block Header: plain .xz, read by any decoder.  Together with XZAMD_F_AUTO_DELTA both analyses run; a Block takes the
+ * BCJ filter when that rule fires and else what the delta rule says -- never two filters.  Blocks that go out stored carry no
+ * filter.  Allowed and declined (XZAMD_OPTIONS_ERROR) exactly where XZAMD_F_AUTO_DELTA is: not with a filter already in front
+ * of LZMA2, XZAMD_F_SEGMENTS, XZAMD_F_SINGLE or XZAMD_F_REPAIR, nor over a kernel layer without the entry points; with
+ * XZAMD_F_VERIFY every Block is its own verification unit.  Without the flag no byte and no launch changes. */
+#define XZAMD_F_AUTO_BCJ 128u
 
 typedef struct {
 	uint64_t unpadded_size;      /* Index record field 1 (block_util.c:45-76) */
@@ -305,6 +318,12 @@ int xzamd_stream_encode_device(xzamd_ctx *ctx,
  * layer without the entry points.  The histograms and choices stay fetchable (XZAMD_DEBUG_DELTA_HIST / _DIST) for inputs of
  * one device batch. */
 int xzamd_auto_delta_device(xzamd_ctx *ctx, const void *d_in, uint64_t in_size, uint64_t block_size, uint32_t *dist_out,
+		uint64_t cap, uint64_t *nblocks, void *stream);
+
+/* The analysis of XZAMD_F_AUTO_BCJ on its own, in the same form: kind_out[b] = the filter id the rule picks for Block b
+ * (XZAMD_BCJ_X86, XZAMD_BCJ_ARM64), 0 = no filter.  The same errors; the histograms, site counts and choices stay fetchable
+ * (XZAMD_DEBUG_BCJ_HIST / _KIND) for inputs of one device batch. */
+int xzamd_auto_bcj_device(xzamd_ctx *ctx, const void *d_in, uint64_t in_size, uint64_t block_size, uint32_t *kind_out,
 		uint64_t cap, uint64_t *nblocks, void *stream);
 
 /* Device .xz decoder (the reference's stream_decoder_mt.c / lzma2_decoder.c / lzma_decoder.c path, SURVEY.md
@@ -562,6 +581,8 @@ int xzamd_trace_read(xzamd_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *coun
 #define XZAMD_DEBUG_CB_START 18     /* the coder's walk: the model at the span start, u16 per probability (padded to 64) */
 #define XZAMD_DEBUG_DELTA_HIST 19   /* XZAMD_F_AUTO_DELTA / xzamd_auto_delta_device, last batch: 11 x 256 x u32 per Block (candidates none, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32) */
 #define XZAMD_DEBUG_DELTA_DIST 20   /* ... the chosen distance per Block, u32 (0 = no filter) */
+#define XZAMD_DEBUG_BCJ_HIST 21     /* XZAMD_F_AUTO_BCJ / xzamd_auto_bcj_device, last batch of nb Blocks: nb x 2 x 2 x 4096 x u32 ([Block][x86, ARM64][operand as stored, absolute][bucket]), then nb x 2 x u32 site counts */
+#define XZAMD_DEBUG_BCJ_KIND 22     /* ... the chosen filter id per Block, u32 (0 = no filter) */
 int xzamd_debug_fetch(xzamd_ctx *ctx, int what, void *host_out, uint64_t bytes);
 
 /* Seeded synthetic corpora used by bench.py and the tests (host memory). */

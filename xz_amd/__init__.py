@@ -26,6 +26,10 @@ F_SINGLE = 32
 F_AUTO_DELTA = 64
 AUTO_DELTA_DISTANCES = (0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32)     # candidates of the automatic delta filter, 0 = none
 DEBUG_DELTA_HIST, DEBUG_DELTA_DIST = 19, 20
+F_AUTO_BCJ = 128
+AUTO_BCJ_KINDS = (4, 0x0A)           # candidates of the automatic BCJ filter: x86, ARM64 (.xz filter ids)
+AUTO_BCJ_BUCKETS = 4096
+DEBUG_BCJ_HIST, DEBUG_BCJ_KIND = 21, 22
 VSTEPS = ("none", "grammar", "decode", "check", "compare")     # XZAMD_VSTEP_*
 NO_BLOCK = 0xFFFFFFFFFFFFFFFF
 BCJ_X86 = 4
@@ -193,6 +197,9 @@ def lib():
         if hasattr(l, "xzamd_auto_delta_device"):       # (an older library lacks the automatic delta filter)
             l.xzamd_auto_delta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32),
                                                   C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        if hasattr(l, "xzamd_auto_bcj_device"):         # (an older library lacks the automatic BCJ filter)
+            l.xzamd_auto_bcj_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32),
+                                                C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         l.xzamd_debug_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         l.xzamd_trace_enable.argtypes = [C.c_void_p, C.c_uint32]
         l.xzamd_trace_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -336,7 +343,7 @@ class Encoder:
 
     def encode(self, data, opts=None, preset=6, block_size=0, check=CHECK_CRC64,
                span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0, repair=False,
-               single=False, auto_delta=False):
+               single=False, auto_delta=False, auto_bcj=False):
         """Encode a CUDA uint8 tensor into an .xz Stream (CUDA uint8 tensor).
 
         Returns (out_tensor_view, block_infos). Runs on torch's current stream.
@@ -354,6 +361,9 @@ class Encoder:
         Checks none / CRC32 / CRC64, no filter in front of LZMA2.
         auto_delta: every Block gets the delta filter the device picks for it from byte histograms, or none
         (XZAMD_F_AUTO_DELTA); for the chain {LZMA2} only, not with single or repair.
+        auto_bcj: every Block gets the BCJ filter (x86 or ARM64) the device picks for it from the entropy of its call
+        operands, or none (XZAMD_F_AUTO_BCJ); the same restrictions.  With auto_delta too a Block takes the BCJ filter when
+        that rule fires, else what the delta rule says.
 
         Every XzAmdError raised here carries `code` (the XZAMD_* value; it used to be None for encode failures) and
         `stream` (what was written: empty unless the failure is a verification defect).
@@ -383,7 +393,8 @@ class Encoder:
         rc = lib().xzamd_stream_encode_device(
             self._ctx, C.c_void_p(data.data_ptr()), n, bs, C.byref(opts), check,
             (F_BLOCKS_ONLY if blocks_only else 0) | (F_VERIFY if verify else 0) | (F_KEEP_RESUME if keep_resume else 0)
-            | (F_REPAIR if repair else 0) | (F_SINGLE if single else 0) | (F_AUTO_DELTA if auto_delta else 0) | flags,
+            | (F_REPAIR if repair else 0) | (F_SINGLE if single else 0) | (F_AUTO_DELTA if auto_delta else 0)
+            | (F_AUTO_BCJ if auto_bcj else 0) | flags,
             C.c_void_p(out.data_ptr()), out.numel(),
             C.byref(out_size), binfo, max(nblocks, 1), C.byref(nb), C.c_void_p(stream))
         if rc != 0:
@@ -420,6 +431,36 @@ class Encoder:
             if rc != 0:
                 raise XzAmdError(f"xzamd_debug_fetch({what}) failed ({rc})", rc)
         return hist, dist
+
+    def choose_bcj(self, data, block_size):
+        """What encode(auto_bcj=True) would pick for every Block of `block_size` bytes of `data` (CUDA uint8 tensor): the
+        list of filter ids (BCJ_X86, BCJ_ARM64), 0 = no filter (xzamd_auto_bcj_device)."""
+        import torch
+        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
+        n = data.numel()
+        cap = max((n + block_size - 1) // block_size, 1) if block_size else 1
+        kind = (C.c_uint32 * cap)()
+        nb = C.c_uint64(0)
+        torch.cuda.current_stream(data.device).synchronize()
+        rc = lib().xzamd_auto_bcj_device(self._ctx, C.c_void_p(data.data_ptr()), n, block_size, kind, cap, C.byref(nb), None)
+        if rc != 0:
+            raise XzAmdError(f"xzamd_auto_bcj_device failed ({rc}): {lib().xzamd_last_error(self._ctx).decode()}", rc)
+        return list(kind)[: nb.value]
+
+    def bcj_histograms(self, nblocks):
+        """What the last choose_bcj / encode(auto_bcj=True) of this context left for the `nblocks` Blocks of its last batch:
+        (uint32 array [nblocks, 2, 2, 4096]: per candidate of AUTO_BCJ_KINDS the histogram of the operands as stored and
+        made absolute, uint32 array [nblocks, 2] of site counts, uint32 array [nblocks] of chosen filter ids)."""
+        import numpy as np
+        words = len(AUTO_BCJ_KINDS) * 2 * AUTO_BCJ_BUCKETS
+        both = np.zeros(nblocks * (words + len(AUTO_BCJ_KINDS)), dtype=np.uint32)
+        kind = np.zeros(nblocks, dtype=np.uint32)
+        for what, a in ((DEBUG_BCJ_HIST, both), (DEBUG_BCJ_KIND, kind)):
+            rc = lib().xzamd_debug_fetch(self._ctx, what, C.c_void_p(a.ctypes.data), a.nbytes)
+            if rc != 0:
+                raise XzAmdError(f"xzamd_debug_fetch({what}) failed ({rc})", rc)
+        hist = both[: nblocks * words].reshape(nblocks, len(AUTO_BCJ_KINDS), 2, AUTO_BCJ_BUCKETS)
+        return hist, both[nblocks * words:].reshape(nblocks, len(AUTO_BCJ_KINDS)), kind
 
     def verify_report(self):
         """The report of this context's last verification (`verify`, or an encode with verify=True) as a dict named like

@@ -240,6 +240,20 @@ int xzk_delta_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32
 int xzk_delta_choose(const uint32_t *d_hist, uint32_t nblocks, uint32_t *d_dist, void *stream);
 int xzk_delta_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t *d_dist,
 		void *stream);
+/* Automatic per-Block BCJ filter (auto_bcj_rule.h).  The host units refer to the three weakly: over a kernel layer without
+ * them XZAMD_F_AUTO_BCJ is XZAMD_OPTIONS_ERROR.
+ * xzk_bcj_stats: d_hist[nblocks][XZAMD_AB_NCAND][2][XZAMD_AB_BUCKETS] (uint32_t) = per candidate (x86, ARM64) the hashed
+ * histograms of every call-site operand of the whole Block as stored and as the filter would store it, d_nsites[nblocks]
+ * [XZAMD_AB_NCAND] = the number of sites (both zeroed first).  xzk_bcj_choose: d_kind[b] = the filter id the rule picks for
+ * Block b (4, 0x0A), 0 = none; with d_dist (the choices of xzk_delta_choose) d_dist[b] = 0 where a BCJ filter is picked.
+ * xzk_bcj_blocks: Block b of d_out = what xzk_x86_bcj / xzk_prefilter(0x0A) write for it where d_kind[b] names that filter;
+ * the other Blocks are d_in (copy != 0) or left as d_out has them (copy == 0: d_out is filled already). */
+int xzk_bcj_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t *d_hist, uint32_t *d_nsites,
+		void *stream);
+int xzk_bcj_choose(const uint32_t *d_hist, const uint32_t *d_nsites, uint32_t n, uint32_t block_size, uint32_t nblocks,
+		uint32_t *d_kind, uint32_t *d_dist, void *stream);
+int xzk_bcj_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t *d_kind,
+		int copy, void *stream);
 /* SHA-256 of every Block (32 bytes each). */
 int xzk_sha256_blocks(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint8_t *d_out32, void *stream);
 /* Block checks: CRC64 (crc32 = 0) or CRC32 (crc32 = 1, zero-extended into d_block_crc). */

@@ -6,6 +6,7 @@
 #include "wave.h"
 #include "bcj_rules.h"
 #include "delta_rule.h"
+#include "auto_bcj_rule.h"
 
 namespace {
 
@@ -18,18 +19,20 @@ namespace {
 // straddle such a position.  So a chunk owner starts at the first such synchronisation point of its
 // chunk and runs to the first one at or after the chunk end (= where the next owner starts): exact,
 // chunk-parallel, and sequential only on input without synchronisation points.
-// `out` already holds a copy of `in`; only converted operands are written.
+// `out` already holds a copy of `in`; only converted operands are written.  With `kind` (the automatic per-Block BCJ
+// filter) only the Blocks whose kind[blk] is this filter's id are filtered; the others stay the copy.
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t BCJ_CHUNK = 2048;
 
 __global__ __launch_bounds__(256) void k_x86_bcj(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
-        uint32_t block_size, uint32_t chunks_per_block, uint32_t nchunks)
+        uint32_t block_size, uint32_t chunks_per_block, uint32_t nchunks, const uint32_t* __restrict__ kind)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nchunks) return;
     const uint32_t blk = t / chunks_per_block, k = t - blk * chunks_per_block;
     const uint32_t bs = blk * block_size;
     if (bs >= n) return;
+    if (kind && kind[blk] != 4u) return;
     const uint32_t size = min(n - bs, block_size);
     if (size < 5) return;
     const uint32_t limit = size - 5;                 // last position the filter examines
@@ -94,9 +97,10 @@ __global__ __launch_bounds__(256) void k_x86_bcj(const uint8_t* __restrict__ in,
 // filter per Block, start offset 0.  Both are stateless given the ORIGINAL bytes (ARM64: every aligned
 // 4-byte instruction on its own, pc = offset inside the Block; delta: byte minus the byte `dist` before it
 // in the Block, zero history), so they are plain data-parallel maps -- one thread per instruction / byte.
+// k_arm64_bcj with `kind`: only the Blocks whose kind[b] is 0x0A, as in k_x86_bcj.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_arm64_bcj(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t n,
-        uint32_t block_size, uint32_t nblocks)
+        uint32_t block_size, uint32_t nblocks, const uint32_t* __restrict__ kind)
 {
     const uint32_t spb = block_size / 4;                      // instruction slots per full Block
     if (spb == 0) return;
@@ -106,6 +110,7 @@ __global__ __launch_bounds__(256) void k_arm64_bcj(const uint8_t* __restrict__ i
         const uint32_t b = (uint32_t)(t / spb), k = (uint32_t)(t - (uint64_t)b * spb);
         const uint32_t bs = b * block_size;
         if (bs >= n) continue;
+        if (kind && kind[b] != 0x0Au) continue;
         const uint32_t len = min(n - bs, block_size) & ~3u;   // arm64.c:26: the tail (size & 3) stays as it is
         const uint32_t pc = k * 4;
         if (pc + 4 > len) continue;
@@ -446,6 +451,124 @@ __global__ __launch_bounds__(256) void k_delta_blocks(const uint8_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
+// Automatic per-Block BCJ filter (auto_bcj_rule.h, DESIGN.md 3.5 "Automatic BCJ"): per Block and candidate the hashed
+// histograms of the call-site operands as they are stored and as the filter would store them, over the WHOLE Block, an
+// integer entropy cost for each, and the choice.  The chosen Blocks are then filtered by the fixed-chain kernels above,
+// which read kind[] (xzk_bcj_blocks).
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t AB_TILE = 4096;        // bytes a workgroup of k_bcj_stats takes per step: 256 threads x 16
+constexpr uint32_t AB_RUN = 16;           // steps per workgroup: 64 KiB of the Block for one clearing and one flush of 32 KiB of LDS
+
+// One workgroup = AB_RUN consecutive tiles of one Block under one candidate (uniform per workgroup: no divergence on
+// it); a thread = 16 bytes of a tile and the 4 bytes behind them, which the operand of an x86 site in its last bytes needs
+// (one 16-byte and one 4-byte load where all 20 lie inside the Block, single bytes at the Block's end; nothing in front is
+// needed, so the Block's start takes the fast path).  The two histograms live in LDS -- 32 KiB and not a byte more, so that five
+// workgroups share a CU's 160 KiB -- and are added to the Block's in global memory once per workgroup; the site count goes
+// there once per wavefront.  hist and nsites must be zero on entry.
+__global__ __launch_bounds__(256) void k_bcj_stats(const uint8_t* __restrict__ in, uint32_t n, uint32_t block_size,
+        uint32_t runs_per_block, uint32_t* __restrict__ hist, uint32_t* __restrict__ nsites)
+{
+    __shared__ uint32_t h[2 * XZAMD_AB_BUCKETS];
+    const uint32_t per_block = runs_per_block * XZAMD_AB_NCAND;
+    const uint32_t blk = blockIdx.x / per_block, r = blockIdx.x - blk * per_block;
+    const uint32_t cand = r / runs_per_block, run = r - cand * runs_per_block;
+    const uint64_t bs = (uint64_t)blk * block_size;
+    if (bs >= n) return;
+    const uint32_t blen = (uint32_t)min((uint64_t)block_size, (uint64_t)n - bs);
+    if ((uint64_t)run * AB_RUN * AB_TILE >= blen) return;
+    const uint8_t* __restrict__ b = in + bs;
+    for (uint32_t i = threadIdx.x; i < 2 * XZAMD_AB_BUCKETS; i += 256) h[i] = 0;
+    __syncthreads();
+    uint32_t mine = 0;
+    for (uint32_t t = run * AB_RUN; t < (run + 1) * AB_RUN; ++t) {
+        const uint64_t o64 = (uint64_t)t * AB_TILE + threadIdx.x * 16u;      // of this thread's 16 bytes in the Block
+        if (o64 >= blen) break;
+        const uint32_t o = (uint32_t)o64;
+        uint32_t x[5];                                    // bytes o .. o + 19 of the Block, zero behind its end
+        if (o + 20 <= blen) {
+            uint4 v;
+            __builtin_memcpy(&v, b + o, 16);
+            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+            __builtin_memcpy(&x[4], b + o + 16, 4);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t p = o + 4 * q + k;
+                    if (p < blen) v |= (uint32_t)b[p] << (8 * k);
+                }
+                x[q] = v;
+            }
+        }
+        if (cand == XZAMD_AB_X86) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const uint32_t c = (x[j / 4] >> (8 * (j & 3))) & 255u;
+                const uint32_t top = (x[(j + 4) / 4] >> (8 * (j & 3))) & 255u;
+                if ((c & 0xFEu) == 0xE8u && (top == 0x00u || top == 0xFFu) && o + j + 4 < blen) {
+                    const int p = j + 1;
+                    const uint32_t rel = (p & 3) == 0 ? x[p / 4]
+                            : (uint32_t)((((uint64_t)x[(p + 3) / 4] << 32) | x[p / 4]) >> (8 * (p & 3)));
+                    atomicAdd(&h[xzamd_ab_hash(rel)], 1u);
+                    atomicAdd(&h[XZAMD_AB_BUCKETS + xzamd_ab_hash(rel + o + j + 5u)], 1u);
+                    ++mine;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t w = x[q], i = o + 4 * q;       // o is a multiple of 16: i mod 4 == 0 inside the Block
+                if ((w >> 26) == 0x25u && i + 3 < blen) {
+                    const uint32_t rel = w & 0x03FFFFFFu;
+                    atomicAdd(&h[xzamd_ab_hash(rel)], 1u);
+                    atomicAdd(&h[XZAMD_AB_BUCKETS + xzamd_ab_hash((rel + (i >> 2)) & 0x03FFFFFFu)], 1u);
+                    ++mine;
+                }
+            }
+        }
+    }
+    const uint32_t wave_sites = wave_sum_dpp(mine);      // (every lane is here: the loop above is left by break only)
+    if ((threadIdx.x & 63u) == 0 && wave_sites) atomicAdd(&nsites[blk * XZAMD_AB_NCAND + cand], wave_sites);
+    __syncthreads();
+    uint32_t* __restrict__ g = hist + ((uint64_t)blk * XZAMD_AB_NCAND + cand) * (2 * XZAMD_AB_BUCKETS);
+    for (uint32_t i = threadIdx.x; i < 2 * XZAMD_AB_BUCKETS; i += 256)
+        if (h[i]) atomicAdd(&g[i], h[i]);
+}
+
+// One wavefront per Block: the four costs S = N * L(N) - sum_v hist[v] * L(hist[v]), the rule, kind[b] = the chosen filter
+// id (0: no filter).  With `dist` (the automatic delta runs too) a Block that gets a BCJ filter loses its delta distance.
+__global__ __launch_bounds__(64) void k_bcj_choose(const uint32_t* __restrict__ hist, const uint32_t* __restrict__ nsites,
+        uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t* __restrict__ kind, uint32_t* __restrict__ dist)
+{
+    const uint32_t blk = blockIdx.x, lane = threadIdx.x;
+    if (blk >= nblocks) return;
+    const uint64_t bs = (uint64_t)blk * block_size;
+    const uint32_t blen = bs >= n ? 0u : (uint32_t)min((uint64_t)block_size, (uint64_t)n - bs);
+    uint64_t S[XZAMD_AB_NCAND][2], N[XZAMD_AB_NCAND];
+    for (uint32_t k = 0; k < XZAMD_AB_NCAND; ++k) {
+        N[k] = nsites[blk * XZAMD_AB_NCAND + k];
+        for (uint32_t w = 0; w < 2; ++w) {
+            const uint32_t* __restrict__ g = hist + (((uint64_t)blk * XZAMD_AB_NCAND + k) * 2 + w) * XZAMD_AB_BUCKETS;
+            uint64_t sum = 0;
+            for (uint32_t v = lane; v < XZAMD_AB_BUCKETS; v += 64) {
+                const uint32_t c = g[v];
+                sum += (uint64_t)c * xzamd_ad_log(c, AD_LOG);
+            }
+            for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor((unsigned long long)sum, s);
+            S[k][w] = xzamd_ab_cost(N[k], sum, AD_LOG);
+        }
+    }
+    if (lane == 0) {
+        const uint64_t S_rel[XZAMD_AB_NCAND] = { S[0][0], S[1][0] }, S_abs[XZAMD_AB_NCAND] = { S[0][1], S[1][1] };
+        const uint32_t kd = xzamd_ab_rule(S_rel, S_abs, N, blen);
+        kind[blk] = kd;
+        if (dist && kd) dist[blk] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // SHA-256 Block check (check/sha256.c:120-189, FIPS 180-4): a serial hash per Block, so one THREAD per
 // Block (Blocks are the parallelism; the default Check, CRC64, stays the fast path).  32 bytes per Block.
 // ------------------------------------------------------------------------------------------
@@ -638,7 +761,7 @@ int xzk_x86_bcj(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t block_
     const uint64_t nch = (uint64_t)cpb * nblocks;
     if (nch == 0 || nch > 0xFFFFFFFFull) return nch ? (int)hipErrorInvalidValue : 0;
     hipLaunchKernelGGL(k_x86_bcj, dim3((uint32_t)((nch + 255) / 256)), dim3(256), 0, st, d_in, d_out, n, block_size, cpb,
-            (uint32_t)nch);
+            (uint32_t)nch, (const uint32_t*)nullptr);
     return (int)hipGetLastError();
 }
 
@@ -652,7 +775,8 @@ int xzk_prefilter(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t bloc
     if (kind == 0x0A) {
         int e = (int)hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, st);
         if (e) return e;
-        hipLaunchKernelGGL(k_arm64_bcj, dim3(grid_for((uint64_t)n / 4 + 1, 256, 65536)), dim3(256), 0, st, d_in, d_out, n, block_size, nblocks);
+        hipLaunchKernelGGL(k_arm64_bcj, dim3(grid_for((uint64_t)n / 4 + 1, 256, 65536)), dim3(256), 0, st, d_in, d_out, n, block_size, nblocks,
+                (const uint32_t*)nullptr);
     } else if (kind == 0x0B) {
         int e = (int)hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, st);
         if (e) return e;
@@ -703,6 +827,54 @@ int xzk_delta_blocks(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t b
     if (block_size == 0 || (uint64_t)nblocks * block_size < n || n > 0xFFFFFFE0u) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_delta_blocks, dim3(grid_for(((uint64_t)n + 15) / 16, 256, 65536)), dim3(256), 0, (hipStream_t)stream_, d_in, d_out,
             n, block_size, d_dist);
+    return (int)hipGetLastError();
+}
+
+int xzk_bcj_stats(const uint8_t* d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t* d_hist, uint32_t* d_nsites,
+        void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    if (nblocks == 0 || n == 0) return 0;
+    if (block_size == 0 || (uint64_t)nblocks * block_size < n) return (int)hipErrorInvalidValue;
+    int e = (int)hipMemsetAsync(d_hist, 0, (uint64_t)nblocks * XZAMD_AB_HIST_WORDS * 4, st);
+    if (!e) e = (int)hipMemsetAsync(d_nsites, 0, (uint64_t)nblocks * XZAMD_AB_NCAND * 4, st);
+    if (e) return e;
+    const uint32_t rpb = (uint32_t)(((uint64_t)block_size + AB_RUN * AB_TILE - 1) / (AB_RUN * AB_TILE));
+    const uint64_t grid = (uint64_t)rpb * XZAMD_AB_NCAND * nblocks;
+    if (grid > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bcj_stats, dim3((uint32_t)grid), dim3(256), 0, st, d_in, n, block_size, rpb, d_hist, d_nsites);
+    return (int)hipGetLastError();
+}
+
+int xzk_bcj_choose(const uint32_t* d_hist, const uint32_t* d_nsites, uint32_t n, uint32_t block_size, uint32_t nblocks,
+        uint32_t* d_kind, uint32_t* d_dist, void* stream_)
+{
+    if (nblocks == 0) return 0;
+    if (block_size == 0) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bcj_choose, dim3(nblocks), dim3(64), 0, (hipStream_t)stream_, d_hist, d_nsites, n, block_size, nblocks,
+            d_kind, d_dist);
+    return (int)hipGetLastError();
+}
+
+// The fixed-chain encoders with kind[] read per Block: x86 over the Blocks of kind 4, ARM64 over those of kind 0x0A, the
+// rest left as the copy.
+int xzk_bcj_blocks(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t* d_kind,
+        int copy, void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    if (n == 0 || nblocks == 0) return 0;
+    if (block_size == 0 || (uint64_t)nblocks * block_size < n || !d_kind) return (int)hipErrorInvalidValue;
+    if (copy) {
+        int e = (int)hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, st);
+        if (e) return e;
+    }
+    const uint32_t cpb = (block_size + BCJ_CHUNK - 1) / BCJ_CHUNK;
+    const uint64_t nch = (uint64_t)cpb * nblocks;
+    if (nch > 0xFFFFFFFFull) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_x86_bcj, dim3((uint32_t)((nch + 255) / 256)), dim3(256), 0, st, d_in, d_out, n, block_size, cpb,
+            (uint32_t)nch, d_kind);
+    hipLaunchKernelGGL(k_arm64_bcj, dim3(grid_for((uint64_t)n / 4 + 1, 256, 65536)), dim3(256), 0, st, d_in, d_out, n, block_size, nblocks,
+            d_kind);
     return (int)hipGetLastError();
 }
 

@@ -13,6 +13,7 @@
 #include "kernels_api.h"
 #include "xzamd_internal.h"
 #include "delta_rule.h"
+#include "auto_bcj_rule.h"
 
 #include <stdio.h>
 #include <pthread.h>
@@ -79,6 +80,8 @@ typedef struct {
 	uint32_t cbytes, hs_fixed;
 	uint32_t hs_delta;           /* XZAMD_F_AUTO_DELTA: header size of a Block that got a delta filter (hs_fixed: of one that got none) */
 	int auto_delta;
+	uint32_t hs_bcj;             /* XZAMD_F_AUTO_BCJ: header size of a Block that got a BCJ filter (x86 and ARM64 take the same two bytes of Filter Flags) */
+	int auto_bcj;
 	int segments;                  /* XZAMD_F_SEGMENTS: per Block only its chunk chain */
 	xzamd_mode m;
 	call_knobs k;
@@ -122,6 +125,7 @@ struct xzamd_ctx {
 	dbuf sym_len[2], sym_dist[2], prior, enc_tab[2], enc_cnt[2];   /* two-phase mode ([2]: one set per pipeline parity) */
 	dbuf tok, chunks, h_chunks;                                    /* coder of the two-phase mode: tokens, chunk table */
 	dbuf dhist, ddist[2];                                          /* XZAMD_F_AUTO_DELTA: histograms of the batch, chosen distance per Block (per pipeline parity) */
+	dbuf bhist, bkind[2];                                          /* XZAMD_F_AUTO_BCJ: histograms of the batch with the site counts behind them, chosen filter id per Block (per pipeline parity) */
 	dbuf resume_sr;                                                /* what the token walk of every encode span started from (resume table asked for) */
 	/* The resume table of the last encode with XZAMD_F_KEEP_RESUME / _VERIFY (kernels_api.h), kept until the next encode;
 	 * not a per-batch buffer: it lives for the call and beyond */
@@ -130,7 +134,7 @@ struct xzamd_ctx {
 	xzamd_verify_report report;                                    /* of the last verification */
 	xzamd_repair_report repair;                                    /* of the last repair */
 	/* pinned host buffers */
-	dbuf h_span_bytes, h_block_crc, h_segs, h_lits, h_span_tab, h_span_cnt[2], h_enc_tab[2], h_enc_cnt[2], h_err[2], h_ddist[2];
+	dbuf h_span_bytes, h_block_crc, h_segs, h_lits, h_span_tab, h_span_cnt[2], h_enc_tab[2], h_enc_cnt[2], h_err[2], h_ddist[2], h_bkind[2];
 	void *evp[2][EV_COUNT];
 	void *ev_total[2];
 	uint32_t trace_cap;
@@ -252,19 +256,19 @@ static void ctx_device_bufs(xzamd_ctx *c, dbuf **d, size_t *nd)
 {
 	dbuf *all[] = { &c->keys_a, &c->keys_b, &c->vals_a, &c->vals_b, &c->rank, &c->sorted_pos,
 		&c->prev2, &c->prev3, &c->prev4, &c->prev8, &c->prev16, &c->prev24, &c->prev32, &c->key64_a, &c->key64_b, &c->sa, &c->sa_rank, &c->sort_tmp,
-		&c->scratch, &c->litp, &c->mlen, &c->mdist, &c->bcj[0], &c->bcj[1], &c->bcjt, &c->est, &c->mtop, &c->order, &c->dhist,
+		&c->scratch, &c->litp, &c->mlen, &c->mdist, &c->bcj[0], &c->bcj[1], &c->bcjt, &c->est, &c->mtop, &c->order, &c->dhist, &c->bhist,
 		&c->sym_len[0], &c->sym_len[1], &c->sym_dist[0], &c->sym_dist[1], &c->tok, &c->cb_log[0], &c->cb_log[1],
 		/* small ones */
 		&c->chunks,
 		&c->span_bytes, &c->strip_crc, &c->block_crc, &c->segs, &c->lits, &c->trace, &c->errw, &c->errw2,
 		&c->totals, &c->span_tab[0], &c->span_tab[1], &c->span_cnt[0], &c->span_cnt[1], &c->prior, &c->enc_tab[0], &c->enc_tab[1], &c->enc_cnt[0], &c->enc_cnt[1],
 		&c->pinfo[0], &c->pinfo[1], &c->snap_sr, &c->part_tab, &c->cb_bnd[0], &c->cb_bnd[1], &c->cb_hdr[0], &c->cb_hdr[1], &c->cb_start[0], &c->cb_start[1],
-		&c->cb_carry[0], &c->cb_carry[1], &c->resume_sr, &c->ddist[0], &c->ddist[1] };
+		&c->cb_carry[0], &c->cb_carry[1], &c->resume_sr, &c->ddist[0], &c->ddist[1], &c->bkind[0], &c->bkind[1] };
 	_Static_assert(sizeof(all) / sizeof(all[0]) <= CTX_NBUF_MAX, "ctx_device_bufs: raise CTX_NBUF_MAX");
 	*nd = sizeof(all) / sizeof(all[0]);
 	memcpy(d, all, sizeof(all));
 }
-#define CTX_NBIG 36      /* the first CTX_NBIG entries of ctx_device_bufs scale with the batch */
+#define CTX_NBIG 37      /* the first CTX_NBIG entries of ctx_device_bufs scale with the batch */
 
 void xzamd_ctx_destroy(xzamd_ctx *c)
 {
@@ -283,7 +287,7 @@ void xzamd_ctx_destroy(xzamd_ctx *c)
 		if (d[i]->p) xzk_free(d[i]->p);
 	if (c->resume_tab.p) xzk_free(c->resume_tab.p);
 	dbuf *h[] = { &c->h_span_bytes, &c->h_block_crc, &c->h_segs, &c->h_lits, &c->h_span_tab, &c->h_span_cnt[0], &c->h_span_cnt[1],
-		&c->h_enc_tab[0], &c->h_enc_tab[1], &c->h_enc_cnt[0], &c->h_enc_cnt[1], &c->h_err[0], &c->h_err[1], &c->h_chunks, &c->h_ddist[0], &c->h_ddist[1] };
+		&c->h_enc_tab[0], &c->h_enc_tab[1], &c->h_enc_cnt[0], &c->h_enc_cnt[1], &c->h_err[0], &c->h_err[1], &c->h_chunks, &c->h_ddist[0], &c->h_ddist[1], &c->h_bkind[0], &c->h_bkind[1] };
 	for (size_t i = 0; i < sizeof(h) / sizeof(h[0]); ++i)
 		if (h[i]->p) xzk_host_free(h[i]->p);
 	for (int i = 0; i < 2 * EV_COUNT; ++i)
@@ -395,6 +399,13 @@ extern int xzk_delta_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size,
 extern int xzk_delta_choose(const uint32_t *d_hist, uint32_t nblocks, uint32_t *d_dist, void *stream) __attribute__((weak));
 extern int xzk_delta_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks,
 		const uint32_t *d_dist, void *stream) __attribute__((weak));
+/* ... and of the automatic BCJ filter: without them XZAMD_F_AUTO_BCJ is XZAMD_OPTIONS_ERROR */
+extern int xzk_bcj_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t *d_hist, uint32_t *d_nsites,
+		void *stream) __attribute__((weak));
+extern int xzk_bcj_choose(const uint32_t *d_hist, const uint32_t *d_nsites, uint32_t n, uint32_t block_size, uint32_t nblocks,
+		uint32_t *d_kind, uint32_t *d_dist, void *stream) __attribute__((weak));
+extern int xzk_bcj_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t *d_kind,
+		int copy, void *stream) __attribute__((weak));
 xzamd_repair_report *xzamd_ctx_repair_report_(xzamd_ctx *c) { return &c->repair; }
 /* A repair re-encodes Blocks on the context of the call it repairs: the kept table leaves the context meanwhile (the
  * re-encode would free it), the stats of the repaired call come back afterwards */
@@ -444,7 +455,8 @@ int xzamd_debug_fetch(xzamd_ctx *c, int what, void *out, uint64_t bytes)
 			: what == XZAMD_DEBUG_PINFO ? &c->pinfo[c->last_par] : what == XZAMD_DEBUG_SNAP_SR ? &c->snap_sr
 			: what == XZAMD_DEBUG_PRIOR ? &c->prior : what == XZAMD_DEBUG_CARRY ? &c->cb_carry[1]
 			: what == XZAMD_DEBUG_CB_HDR ? &c->cb_hdr[1] : what == XZAMD_DEBUG_CB_START ? &c->cb_start[1]
-			: what == XZAMD_DEBUG_DELTA_HIST ? &c->dhist : what == XZAMD_DEBUG_DELTA_DIST ? &c->ddist[c->last_par] : NULL;
+			: what == XZAMD_DEBUG_DELTA_HIST ? &c->dhist : what == XZAMD_DEBUG_DELTA_DIST ? &c->ddist[c->last_par]
+			: what == XZAMD_DEBUG_BCJ_HIST ? &c->bhist : what == XZAMD_DEBUG_BCJ_KIND ? &c->bkind[c->last_par] : NULL;
 	if (!b || !b->p || b->cap < bytes)
 		return XZAMD_PROG_ERROR;
 	xzk_set_device(c->device);
@@ -561,6 +573,16 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		if (flags & XZAMD_F_REPAIR)
 			return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: not with XZAMD_F_REPAIR (the repair plans Block Headers from one chain)", 0);
 	}
+	if (flags & XZAMD_F_AUTO_BCJ) {
+		if (!xzk_bcj_stats || !xzk_bcj_choose || !xzk_bcj_blocks)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: this build has no kernels for it", 0);
+		if (opt->bcj != 0)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: the chain already has a filter in front of LZMA2", 0);
+		if (flags & XZAMD_F_SEGMENTS)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: Blocks only -- the segments of one Block share its chain", 0);
+		if (flags & XZAMD_F_REPAIR)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: not with XZAMD_F_REPAIR (the repair plans Block Headers from one chain)", 0);
+	}
 	if (chains && (!(flags & XZAMD_F_SEGMENTS) || !xzamd_chains_encoded_))
 		return fail(c, XZAMD_OPTIONS_ERROR, "chains: this build has no unit for bare chunk chains", 0);
 	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_SEGMENTS) && !chains)
@@ -624,6 +646,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	{
 		double per_byte = xzamd_work_bytes_per_byte_(opt);
 		if (flags & XZAMD_F_AUTO_DELTA) per_byte += xzamd_auto_delta_bytes_per_byte_(block_size);
+		if (flags & XZAMD_F_AUTO_BCJ) per_byte += xzamd_auto_bcj_bytes_per_byte_(block_size, (flags & XZAMD_F_AUTO_DELTA) != 0);
 		/* the resume table (only when asked for): one record per encode-span slot, for the whole call */
 		if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && J->m.two)
 			per_byte += (double)(XZAMD_RESUME_BYTES(J->m.model_slots) + 32u) * (double)(block_size / XZAMD_ENC_MIN_LEN + 1) / (double)block_size;
@@ -650,6 +673,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	J->cpb = (uint32_t)((block_size + XZAMD_EST_CHUNK - 1) / XZAMD_EST_CHUNK);
 	J->filtered = opt->bcj != 0;          /* any filter in front of LZMA2: the encoder reads a filtered copy */
 	J->auto_delta = (flags & XZAMD_F_AUTO_DELTA) != 0;     /* ... or the copy in which every Block has the filter chosen for it */
+	J->auto_bcj = (flags & XZAMD_F_AUTO_BCJ) != 0;
 	/* Two-stream pipeline (two-phase mode): the back end of batch i -- range coder, checks, sizes, gather -- runs on the
 	 * second stream while the front end of batch i + 1 -- match structures, plan, parse -- runs on the caller's: the coder
 	 * is a few thousand latency-bound wavefronts, the structure build is HBM-bound, they share the GPU well.  The
@@ -681,6 +705,11 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		xzamd_lzma_options view = *opt;
 		view.bcj = XZAMD_FILTER_DELTA(1);
 		J->hs_delta = xzamd_block_header_size_(J->bound, block_size, &view);
+	}
+	if (J->auto_bcj) {
+		xzamd_lzma_options view = *opt;
+		view.bcj = XZAMD_BCJ_X86;
+		J->hs_bcj = xzamd_block_header_size_(J->bound, block_size, &view);
 	}
 	J->check = check;
 	J->dbyte = xzamd_dict_size_byte_(opt->dict_size);
@@ -866,7 +895,12 @@ static int batch_reserve(xzamd_ctx *c, const job_env *J, const batch_run *B, int
 	NEED(lits, B->max_lits, 0);
 	NEED(h_segs, B->max_segs * sizeof(xzamd_copy_seg), 1);
 	NEED(h_lits, B->max_lits, 1);
-	if (J->filtered || J->auto_delta) NEED(bcj[par], n + 16, 0);
+	if (J->filtered || J->auto_delta || J->auto_bcj) NEED(bcj[par], n + 16, 0);
+	if (J->auto_bcj) {
+		NEED(bhist, 4ull * (XZAMD_AB_HIST_WORDS + XZAMD_AB_NCAND) * nb, 0);
+		NEED(bkind[par], 4 * nb, 0);
+		NEED(h_bkind[par], 4 * nb + 16, 1);
+	}
 	if (J->auto_delta) {
 		NEED(dhist, 4ull * XZAMD_AD_HIST_WORDS * nb, 0);
 		NEED(ddist[par], 4 * nb, 0);
@@ -1088,6 +1122,13 @@ static int layout_block(xzamd_ctx *c, job_env *J, const batch_run *B, plan *pl, 
 		if (d > XZAMD_AD_MAXDIST)
 			return fail(c, XZAMD_PROG_ERROR, "automatic delta: distance out of range", 0);
 		if (d != 0) { bopt.bcj = XZAMD_FILTER_DELTA(d); hs_coded = J->hs_delta; }
+	}
+	if (J->auto_bcj) {
+		/* (the BCJ rule goes first: where it fires the device has cleared the Block's delta distance) */
+		const uint32_t kd = ((const uint32_t *)c->h_bkind[par].p)[b];
+		if (kd != 0 && kd != XZAMD_BCJ_X86 && kd != XZAMD_BCJ_ARM64)
+			return fail(c, XZAMD_PROG_ERROR, "automatic bcj: filter id out of range", 0);
+		if (kd != 0) { bopt.bcj = kd; hs_coded = J->hs_bcj; }
 	}
 	uint64_t unp;
 	uint8_t tail[48];
@@ -1346,16 +1387,25 @@ static int front_input(xzamd_ctx *c, const job_env *J, batch_run *B, void *st)
 		}
 		B->enc_in = X;
 	}
-	if (J->auto_delta) {
+	if (J->auto_delta || J->auto_bcj) {
 		/* statistic, choice and filter stay on the device, in stream order in front of the structure build; the choices
-		 * travel to the host behind them and are there when the layout (which waits for this stream's tables) reads them */
+		 * travel to the host behind them and are there when the layout (which waits for this stream's tables) reads them.
+		 * With both analyses the BCJ choice clears the delta distance of the Blocks it takes before the delta stage copies
+		 * or filters every Block, and the BCJ stage then only patches its Blocks in that copy. */
 		uint8_t *const X = (uint8_t *)c->bcj[B->par].p;
-		uint32_t *const dist = (uint32_t *)c->ddist[B->par].p;
-		int e = xzk_delta_stats(in, n, bs, nb, (uint32_t *)c->dhist.p, st);
-		if (!e) e = xzk_delta_choose((const uint32_t *)c->dhist.p, nb, dist, st);
-		if (!e) e = xzk_delta_blocks(in, X, n, bs, nb, dist, st);
-		if (!e) e = xzk_d2h(c->h_ddist[B->par].p, dist, 4ull * nb, st);
-		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic delta filter", e);
+		uint32_t *const dist = J->auto_delta ? (uint32_t *)c->ddist[B->par].p : NULL;
+		uint32_t *const kind = J->auto_bcj ? (uint32_t *)c->bkind[B->par].p : NULL;
+		uint32_t *const bh = (uint32_t *)c->bhist.p;
+		int e = 0;
+		if (dist) e = xzk_delta_stats(in, n, bs, nb, (uint32_t *)c->dhist.p, st);
+		if (!e && dist) e = xzk_delta_choose((const uint32_t *)c->dhist.p, nb, dist, st);
+		if (!e && kind) e = xzk_bcj_stats(in, n, bs, nb, bh, bh + (uint64_t)XZAMD_AB_HIST_WORDS * nb, st);
+		if (!e && kind) e = xzk_bcj_choose(bh, bh + (uint64_t)XZAMD_AB_HIST_WORDS * nb, n, bs, nb, kind, dist, st);
+		if (!e && dist) e = xzk_delta_blocks(in, X, n, bs, nb, dist, st);
+		if (!e && kind) e = xzk_bcj_blocks(in, X, n, bs, nb, kind, dist == NULL, st);
+		if (!e && dist) e = xzk_d2h(c->h_ddist[B->par].p, dist, 4ull * nb, st);
+		if (!e && kind) e = xzk_d2h(c->h_bkind[B->par].p, kind, 4ull * nb, st);
+		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic per-Block filter", e);
 		B->enc_in = X;
 	}
 	return XZAMD_OK;
@@ -1625,6 +1675,8 @@ int xzamd_stream_encode_device(xzamd_ctx *c,
 		return fail(c, XZAMD_OPTIONS_ERROR, "unknown flag", 0);
 	if (c && (flags & XZAMD_F_SINGLE) && (flags & XZAMD_F_AUTO_DELTA))
 		return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: Blocks only -- the single Block of XZAMD_F_SINGLE has one chain", 0);
+	if (c && (flags & XZAMD_F_SINGLE) && (flags & XZAMD_F_AUTO_BCJ))
+		return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: Blocks only -- the single Block of XZAMD_F_SINGLE has one chain", 0);
 	if (c && (flags & XZAMD_F_SINGLE)) {
 		if (!xzamd_single_encode_)
 			return fail(c, XZAMD_OPTIONS_ERROR, "single: this build has no unit for bare chunk chains", 0);
@@ -1670,6 +1722,46 @@ int xzamd_auto_delta_device(xzamd_ctx *c, const void *d_in_, uint64_t in_size, u
 		if (!e) e = xzk_d2h(dist_out + b0, c->ddist[0].p, 4ull * nb, st);
 		if (!e) e = xzk_sync(st);
 		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic delta analysis", e);
+	}
+	return XZAMD_OK;
+}
+
+/* The analysis of XZAMD_F_AUTO_BCJ on its own, in the same form */
+int xzamd_auto_bcj_device(xzamd_ctx *c, const void *d_in_, uint64_t in_size, uint64_t block_size, uint32_t *kind_out, uint64_t cap,
+		uint64_t *nblocks_out, void *stream)
+{
+	if (!c || (!d_in_ && in_size) || !nblocks_out || (!kind_out && cap))
+		return XZAMD_PROG_ERROR;
+	c->err[0] = 0;
+	if (!xzk_bcj_stats || !xzk_bcj_choose)
+		return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: this build has no kernels for it", 0);
+	if (block_size == 0 || block_size >= (1ull << 31))
+		return fail(c, XZAMD_OPTIONS_ERROR, "block_size must be 1 .. 2 GiB - 1", 0);
+	const uint64_t total = (in_size + block_size - 1) / block_size;
+	*nblocks_out = total;
+	if (total > cap)
+		return fail(c, XZAMD_BUF_ERROR, "kind_out too small", 0);
+	if (c->pend.active)
+		(void)pend_complete(c);      /* (its result is the deferred call's) */
+	void *st = stream ? stream : c->own_stream;
+	int e = xzk_set_device(c->device);
+	if (e) return fail(c, XZAMD_DEVICE_ERROR, "hipSetDevice", e);
+	uint64_t max_blocks = ((1ull << 31) - 1) / block_size;
+	if (max_blocks > (1u << 14)) max_blocks = 1u << 14;      /* (64 KiB of histograms per Block) */
+	c->last_par = 0;
+	for (uint64_t b0 = 0; b0 < total; b0 += max_blocks) {
+		const uint64_t nb = total - b0 < max_blocks ? total - b0 : max_blocks;
+		const uint64_t off = b0 * block_size;
+		const uint64_t n = in_size - off < nb * block_size ? in_size - off : nb * block_size;
+		int r = dgrow(c, &c->bhist, 4ull * (XZAMD_AB_HIST_WORDS + XZAMD_AB_NCAND) * nb, 0);
+		if (!r) r = dgrow(c, &c->bkind[0], 4 * nb, 0);
+		if (r) return r;
+		uint32_t *const bh = (uint32_t *)c->bhist.p;
+		e = xzk_bcj_stats((const uint8_t *)d_in_ + off, (uint32_t)n, (uint32_t)block_size, (uint32_t)nb, bh, bh + XZAMD_AB_HIST_WORDS * nb, st);
+		if (!e) e = xzk_bcj_choose(bh, bh + XZAMD_AB_HIST_WORDS * nb, (uint32_t)n, (uint32_t)block_size, (uint32_t)nb, (uint32_t *)c->bkind[0].p, NULL, st);
+		if (!e) e = xzk_d2h(kind_out + b0, c->bkind[0].p, 4ull * nb, st);
+		if (!e) e = xzk_sync(st);
+		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic bcj analysis", e);
 	}
 	return XZAMD_OK;
 }

@@ -5,6 +5,7 @@
  */
 #include "xzamd_internal.h"
 #include "delta_rule.h"
+#include "auto_bcj_rule.h"
 
 #include <string.h>
 
@@ -156,4 +157,11 @@ double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt)
 double xzamd_auto_delta_bytes_per_byte_(uint64_t block_size)
 {
 	return 2.0 + 4.0 * XZAMD_AD_HIST_WORDS / (double)(block_size ? block_size : 1);
+}
+
+/* What XZAMD_F_AUTO_BCJ adds: the filtered copy (unless the automatic delta has it already) and the four histograms and two
+ * site counts of every Block. */
+double xzamd_auto_bcj_bytes_per_byte_(uint64_t block_size, int with_auto_delta)
+{
+	return (with_auto_delta ? 0.0 : 2.0) + 4.0 * (XZAMD_AB_HIST_WORDS + XZAMD_AB_NCAND) / (double)(block_size ? block_size : 1);
 }

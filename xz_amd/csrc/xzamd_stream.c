@@ -140,6 +140,7 @@ struct lzma_internal_s {
 	uint64_t segment_env;        /* XZAMD_SEGMENT_KIB << 10, 0 = lzma_mt_block_size of the chain */
 	int repair;                  /* XZAMD_REPAIR=1 (read at init): every job runs with XZAMD_F_REPAIR -- on its Blocks, or in single mode on
 	                              * the chains of its segments -- and is finished before the next one is launched */
+	int auto_bcj;                /* XZAMD_AUTO_BCJ=1 (read at init), likewise: every such job runs with XZAMD_F_AUTO_BCJ */
 	int auto_delta;              /* XZAMD_AUTO_DELTA=1 (read at init) on the plain chain {LZMA2}: every job runs with XZAMD_F_AUTO_DELTA */
 };
 
@@ -352,7 +353,8 @@ static lzma_ret job_launch(lzma_internal *in, devslot *d, job *j, int io, int *r
 	if (!injected && !(xzk_h2d(b->d_in, j->stage, n, cs) || xzk_sync(cs)) && (vlog("uploaded", j), 1))
 		*rc_out = xzamd_encode_device_(d->ctx, b->d_in, n, in->block_size, &j->opt, in->check,
 				in->single ? (in->repair ? XZAMD_F_SEGMENTS | XZAMD_F_CHAINS_ | XZAMD_F_REPAIR : XZAMD_F_SEGMENTS) : in->repair ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_REPAIR
-						: (in->auto_delta && j->opt.bcj == 0) ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_AUTO_DELTA : XZAMD_F_BLOCKS_ONLY,
+						: j->opt.bcj == 0 ? XZAMD_F_BLOCKS_ONLY | (in->auto_delta ? XZAMD_F_AUTO_DELTA : 0u) | (in->auto_bcj ? XZAMD_F_AUTO_BCJ : 0u)
+						: XZAMD_F_BLOCKS_ONLY,
 				b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
 				&j->nblocks, NULL, ((nd && *nd == '1') || in->repair) ? NULL : deferred);
 	return LZMA_OK;
@@ -692,6 +694,9 @@ static lzma_ret encoder_init(lzma_stream *strm, lzma_ret r, const xzamd_lzma_opt
 		 * not apply -- the single-Block encoder, repaired jobs, and (per job: lzma_filters_update) a chain with filters */
 		const char *ad = getenv("XZAMD_AUTO_DELTA");
 		in->auto_delta = ad && *ad == '1' && !single && !in->repair;
+		/* XZAMD_AUTO_BCJ=1: the per-Block BCJ filter, with the same exclusions */
+		const char *ab = getenv("XZAMD_AUTO_BCJ");
+		in->auto_bcj = ab && *ab == '1' && !single && !in->repair;
 	}
 	in->sequence = ISEQ_RUN;
 	in->sseq = SEQ_HEADER;

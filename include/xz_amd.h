@@ -297,6 +297,17 @@ void xzamd_get_stats(const xzamd_ctx *ctx, xzamd_stats *out);
  * of LZMA2, XZAMD_F_SEGMENTS, XZAMD_F_SINGLE or XZAMD_F_REPAIR, nor over a kernel layer without the entry points; with
  * XZAMD_F_VERIFY every Block is its own verification unit.  Without the flag no byte and no launch changes. */
 #define XZAMD_F_AUTO_BCJ 128u
+/* XZAMD_F_AUTO_LCLP: AUTOMATIC PER-BLOCK LITERAL CONTEXT (DESIGN.md 3.5 "Automatic literal context").  For every Block the
+ * device counts one joint histogram [offset & 7][byte in front >> 5][byte] over the sample set of the automatic delta, of the
+ * bytes LZMA2 codes (behind the Block's filters, chosen or fixed), prices every (lc, lp) with lc <= 3, lp <= 3 and
+ * lc + lp <= opt->lc + opt->lp by the integer order-0 entropy of the bytes under its contexts plus 12 bits per used (context,
+ * byte) cell, and parses and codes the Block with the cheapest pair when that is at least an eighth of a bit per byte below
+ * the job's own; else with opt->lc / opt->lp.  pb is never chosen.  The pair stands in the properties byte of the Block's
+ * LZMA2 chunks, not in its Block Header: plain .xz, read by any decoder.  A job with lc or lp of 4 keeps its pair everywhere.
+ * Allowed with every filter chain, XZAMD_F_AUTO_DELTA / _AUTO_BCJ, XZAMD_F_BLOCKS_ONLY, _KEEP_RESUME and _VERIFY (the resume
+ * records carry the Block's pair), every Check and every preset.  XZAMD_OPTIONS_ERROR with XZAMD_F_SEGMENTS, XZAMD_F_SINGLE or
+ * XZAMD_F_REPAIR, and over a kernel layer without the entry points.  Without the flag no byte this library writes changes. */
+#define XZAMD_F_AUTO_LCLP 256u
 
 typedef struct {
 	uint64_t unpadded_size;      /* Index record field 1 (block_util.c:45-76) */
@@ -325,6 +336,12 @@ int xzamd_auto_delta_device(xzamd_ctx *ctx, const void *d_in, uint64_t in_size, 
  * (XZAMD_DEBUG_BCJ_HIST / _KIND) for inputs of one device batch. */
 int xzamd_auto_bcj_device(xzamd_ctx *ctx, const void *d_in, uint64_t in_size, uint64_t block_size, uint32_t *kind_out,
 		uint64_t cap, uint64_t *nblocks, void *stream);
+
+/* The analysis of XZAMD_F_AUTO_LCLP on its own, in the same form, on the bytes at d_in as they are: props_out[b] =
+ * lc | lp << 8 the rule picks for Block b of a job with (lc, lp).  The same errors, and XZAMD_OPTIONS_ERROR for lc + lp > 4; the
+ * histograms and choices stay fetchable (XZAMD_DEBUG_LCLP_HIST / _PROPS) for inputs of one device batch. */
+int xzamd_auto_lclp_device(xzamd_ctx *ctx, const void *d_in, uint64_t in_size, uint64_t block_size, uint32_t lc, uint32_t lp,
+		uint32_t *props_out, uint64_t cap, uint64_t *nblocks, void *stream);
 
 /* Device .xz decoder (the reference's stream_decoder_mt.c / lzma2_decoder.c / lzma_decoder.c path, SURVEY.md
  * 8f.3): decode a single-Stream .xz file resident in device memory into d_out (trailing bytes, Stream Padding or a second
@@ -583,6 +600,8 @@ int xzamd_trace_read(xzamd_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *coun
 #define XZAMD_DEBUG_DELTA_DIST 20   /* ... the chosen distance per Block, u32 (0 = no filter) */
 #define XZAMD_DEBUG_BCJ_HIST 21     /* XZAMD_F_AUTO_BCJ / xzamd_auto_bcj_device, last batch of nb Blocks: nb x 2 x 2 x 4096 x u32 ([Block][x86, ARM64][operand as stored, absolute][bucket]), then nb x 2 x u32 site counts */
 #define XZAMD_DEBUG_BCJ_KIND 22     /* ... the chosen filter id per Block, u32 (0 = no filter) */
+#define XZAMD_DEBUG_LCLP_HIST 23    /* XZAMD_F_AUTO_LCLP / xzamd_auto_lclp_device, last batch: 8 x 8 x 256 x u32 per Block ([offset & 7][byte in front >> 5][byte]); whole Blocks only */
+#define XZAMD_DEBUG_LCLP_PROPS 24   /* ... the chosen lc | lp << 8 per Block, u32 */
 int xzamd_debug_fetch(xzamd_ctx *ctx, int what, void *host_out, uint64_t bytes);
 
 /* Seeded synthetic corpora used by bench.py and the tests (host memory). */

@@ -27,6 +27,8 @@ F_AUTO_DELTA = 64
 AUTO_DELTA_DISTANCES = (0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32)     # candidates of the automatic delta filter, 0 = none
 DEBUG_DELTA_HIST, DEBUG_DELTA_DIST = 19, 20
 F_AUTO_BCJ = 128
+F_AUTO_LCLP = 256
+DEBUG_LCLP_HIST, DEBUG_LCLP_PROPS = 23, 24
 AUTO_BCJ_KINDS = (4, 0x0A)           # candidates of the automatic BCJ filter: x86, ARM64 (.xz filter ids)
 AUTO_BCJ_BUCKETS = 4096
 DEBUG_BCJ_HIST, DEBUG_BCJ_KIND = 21, 22
@@ -197,6 +199,9 @@ def lib():
         if hasattr(l, "xzamd_auto_delta_device"):       # (an older library lacks the automatic delta filter)
             l.xzamd_auto_delta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32),
                                                   C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        if hasattr(l, "xzamd_auto_lclp_device"):        # (an older library lacks the automatic literal context)
+            l.xzamd_auto_lclp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         if hasattr(l, "xzamd_auto_bcj_device"):         # (an older library lacks the automatic BCJ filter)
             l.xzamd_auto_bcj_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32),
                                                 C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
@@ -343,7 +348,7 @@ class Encoder:
 
     def encode(self, data, opts=None, preset=6, block_size=0, check=CHECK_CRC64,
                span_size=None, blocks_only=False, out=None, verify=False, keep_resume=False, flags=0, repair=False,
-               single=False, auto_delta=False, auto_bcj=False):
+               single=False, auto_delta=False, auto_bcj=False, auto_lclp=False):
         """Encode a CUDA uint8 tensor into an .xz Stream (CUDA uint8 tensor).
 
         Returns (out_tensor_view, block_infos). Runs on torch's current stream.
@@ -364,6 +369,9 @@ class Encoder:
         auto_bcj: every Block gets the BCJ filter (x86 or ARM64) the device picks for it from the entropy of its call
         operands, or none (XZAMD_F_AUTO_BCJ); the same restrictions.  With auto_delta too a Block takes the BCJ filter when
         that rule fires, else what the delta rule says.
+        auto_lclp: every Block is parsed and coded with the literal context (lc, lp) the device picks for it from a joint
+        histogram of its bytes -- never more literal coders than opts.lc + opts.lp, pb stays (XZAMD_F_AUTO_LCLP); with
+        any filter chain and with auto_delta / auto_bcj (the statistic is taken behind the filters), not with single or repair.
 
         Every XzAmdError raised here carries `code` (the XZAMD_* value; it used to be None for encode failures) and
         `stream` (what was written: empty unless the failure is a verification defect).
@@ -394,7 +402,7 @@ class Encoder:
             self._ctx, C.c_void_p(data.data_ptr()), n, bs, C.byref(opts), check,
             (F_BLOCKS_ONLY if blocks_only else 0) | (F_VERIFY if verify else 0) | (F_KEEP_RESUME if keep_resume else 0)
             | (F_REPAIR if repair else 0) | (F_SINGLE if single else 0) | (F_AUTO_DELTA if auto_delta else 0)
-            | (F_AUTO_BCJ if auto_bcj else 0) | flags,
+            | (F_AUTO_BCJ if auto_bcj else 0) | (F_AUTO_LCLP if auto_lclp else 0) | flags,
             C.c_void_p(out.data_ptr()), out.numel(),
             C.byref(out_size), binfo, max(nblocks, 1), C.byref(nb), C.c_void_p(stream))
         if rc != 0:
@@ -403,6 +411,35 @@ class Encoder:
             err.stream = out[: out_size.value]
             raise err
         return out[: out_size.value], list(binfo)[: nb.value]
+
+    def choose_lclp(self, data, block_size, lc=3, lp=0):
+        """What encode(auto_lclp=True) of a job with (lc, lp) and no filter would pick for every Block of `block_size` bytes
+        of `data` (CUDA uint8 tensor): the list of (lc, lp) pairs (xzamd_auto_lclp_device)."""
+        import torch
+        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
+        n = data.numel()
+        cap = max((n + block_size - 1) // block_size, 1) if block_size else 1
+        props = (C.c_uint32 * cap)()
+        nb = C.c_uint64(0)
+        torch.cuda.current_stream(data.device).synchronize()
+        rc = lib().xzamd_auto_lclp_device(self._ctx, C.c_void_p(data.data_ptr()), n, block_size, lc, lp, props, cap,
+                                          C.byref(nb), None)
+        if rc != 0:
+            raise XzAmdError(f"xzamd_auto_lclp_device failed ({rc}): {lib().xzamd_last_error(self._ctx).decode()}", rc)
+        return [(v & 255, v >> 8) for v in list(props)[: nb.value]]
+
+    def lclp_stats(self, nblocks):
+        """The joint histograms and choices the last choose_lclp / encode(auto_lclp=True) of this context left for the
+        `nblocks` Blocks of its last batch: (uint32 array [nblocks, 8, 8, 256] indexed [offset & 7][byte in front >> 5][byte],
+        list of (lc, lp))."""
+        import numpy as np
+        hist = np.zeros((nblocks, 8, 8, 256), dtype=np.uint32)
+        props = np.zeros(nblocks, dtype=np.uint32)
+        for what, a in ((DEBUG_LCLP_HIST, hist), (DEBUG_LCLP_PROPS, props)):
+            rc = lib().xzamd_debug_fetch(self._ctx, what, C.c_void_p(a.ctypes.data), a.nbytes)
+            if rc != 0:
+                raise XzAmdError(f"xzamd_debug_fetch({what}) failed ({rc})", rc)
+        return hist, [(int(v) & 255, int(v) >> 8) for v in props]
 
     def choose_delta(self, data, block_size):
         """What encode(auto_delta=True) would pick for every Block of `block_size` bytes of `data` (CUDA uint8 tensor): the

@@ -93,6 +93,8 @@ typedef struct {
 	                                "not merged: the rest of the Block is not carried" fall-back on ordinary data */
 	uint32_t *resume_sr;         /* optional (resume table asked for), 8 x u32 per encode-span slot: what the token walk (k_model_syms)
 	                                actually started from: [0] coder state, [1..4] rep distances, [5] XZAMD_RK_* */
+	const uint32_t *props_tab;   /* XZAMD_F_AUTO_LCLP: lc | lp << 8 of every Block of the batch (never more literal coders than the job's lc + lp:
+	                                every stride stays the job's, a Block with fewer uses the front of its slots); NULL = the job's lc / lp */
 } xzamd_span_args;
 #define XZAMD_ITER_PARTIAL 1u       /* parse only the first part (part_tab) of every piece but the seed */
 #define XZAMD_ITER_SNAP 2u          /* every piece but the seed starts from its snapshot (else: the seed's prior + walk + pre-roll) */
@@ -254,6 +256,14 @@ int xzk_bcj_choose(const uint32_t *d_hist, const uint32_t *d_nsites, uint32_t n,
 		uint32_t *d_kind, uint32_t *d_dist, void *stream);
 int xzk_bcj_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t *d_kind,
 		int copy, void *stream);
+/* Automatic per-Block literal context (lclp_rule.h).  The host units refer to the three weakly: over a kernel layer without
+ * them XZAMD_F_AUTO_LCLP is XZAMD_OPTIONS_ERROR.
+ * xzk_lclp_stats: d_hist[nblocks][8][8][256] (uint32_t) = H[pos & 7][prev >> 5][byte] over every Block's sample set (zeroed
+ * first).  xzk_lclp_choose: d_props[b] = lc | lp << 8 the rule picks for Block b of a job with (lc, lp).  xzk_lclp_read: the
+ * histograms and / or choices of nblocks Blocks into host memory (either may be NULL), synchronously: for tests. */
+int xzk_lclp_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t *d_hist, void *stream);
+int xzk_lclp_choose(const uint32_t *d_hist, uint32_t nblocks, uint32_t lc, uint32_t lp, uint32_t *d_props, void *stream);
+int xzk_lclp_read(const uint32_t *d_hist, const uint32_t *d_props, uint32_t nblocks, uint32_t *h_hist, uint32_t *h_props, void *stream);
 /* SHA-256 of every Block (32 bytes each). */
 int xzk_sha256_blocks(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint8_t *d_out32, void *stream);
 /* Block checks: CRC64 (crc32 = 0) or CRC32 (crc32 = 1, zero-extended into d_block_crc). */

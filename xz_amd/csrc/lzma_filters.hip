@@ -7,6 +7,7 @@
 #include "bcj_rules.h"
 #include "delta_rule.h"
 #include "auto_bcj_rule.h"
+#include "lclp_rule.h"
 
 namespace {
 
@@ -569,6 +570,120 @@ __global__ __launch_bounds__(64) void k_bcj_choose(const uint32_t* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------
+// Automatic per-Block literal context (lclp_rule.h, DESIGN.md 3.5 "Automatic literal context"): the joint histogram
+// H[pos & 7][prev >> 5][byte] of every Block's sample set, and per Block the costs of the candidate (lc, lp) pairs and
+// the choice.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t LL_RUN = 8;            // sample windows per workgroup of k_lclp_stats: two per wavefront
+
+// One workgroup = LL_RUN consecutive sample windows of one Block, one WAVEFRONT = one window at a time (a lane = 16 bytes
+// in each of four passes, one 16-byte load where they lie inside the Block; the byte in front is one more load of the same
+// line).  The whole joint table is privatised in LDS as 16-bit counters, two to a word: a workgroup counts at most
+// LL_RUN * 4096 = 32,768 bytes, so no counter can carry into its neighbour, and 32 KiB of LDS leave room for five
+// workgroups per CU.  The table is added to the Block's in global memory once per workgroup.  hist must be zero on entry.
+static_assert(LL_RUN * XZAMD_AD_WINDOW < 65536u, "k_lclp_stats: 16-bit LDS counters");
+__global__ __launch_bounds__(256) void k_lclp_stats(const uint8_t* __restrict__ in, uint32_t n, uint32_t block_size,
+        uint32_t runs_per_block, uint32_t* __restrict__ hist)
+{
+    __shared__ uint32_t h[XZAMD_LL_HIST_WORDS / 2];
+    const uint32_t blk = blockIdx.x / runs_per_block, run = blockIdx.x - blk * runs_per_block;
+    const uint64_t bs = (uint64_t)blk * block_size;
+    if (bs >= n) return;
+    const uint32_t blen = (uint32_t)min((uint64_t)block_size, (uint64_t)n - bs);
+    const uint8_t* __restrict__ b = in + bs;
+    for (uint32_t i = threadIdx.x; i < XZAMD_LL_HIST_WORDS / 2; i += 256) h[i] = 0;
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    for (uint32_t w = run * LL_RUN + wave; w < (run + 1) * LL_RUN; w += 4) {
+        const uint64_t w0 = (uint64_t)w * XZAMD_AD_PERIOD;
+        if (w0 >= blen) break;
+#pragma unroll
+        for (uint32_t q = 0; q < XZAMD_AD_WINDOW / 1024u; ++q) {
+            const uint64_t o64 = w0 + q * 1024u + lane * 16u;      // of this lane's 16 bytes in the Block
+            if (o64 >= blen) continue;
+            const uint32_t o = (uint32_t)o64;
+            const uint32_t cnt = min(16u, blen - o);          // sampled bytes of this lane
+            uint32_t x[4] = { 0, 0, 0, 0 };
+            if (cnt == 16) {
+                uint4 v;
+                __builtin_memcpy(&v, b + o, 16);
+                x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+            } else {
+                for (uint32_t j = 0; j < cnt; ++j) x[j / 4] |= (uint32_t)b[o + j] << (8 * (j & 3));
+            }
+            uint32_t prev = o != 0 ? (uint32_t)b[o - 1] : 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < 16; ++j) {
+                if (j < cnt) {
+                    const uint32_t cur = (x[j / 4] >> (8 * (j & 3))) & 255u;
+                    const uint32_t idx = ((((o + j) & 7u) * 8u + (prev >> 5)) << 8) + cur;
+                    atomicAdd(&h[idx >> 1], 1u << (16 * (idx & 1u)));
+                    prev = cur;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* __restrict__ g = hist + (uint64_t)blk * XZAMD_LL_HIST_WORDS;
+    for (uint32_t i = threadIdx.x; i < XZAMD_LL_HIST_WORDS / 2; i += 256) {
+        const uint32_t v = h[i];
+        if (v & 0xFFFFu) atomicAdd(&g[2 * i], v & 0xFFFFu);
+        if (v >> 16) atomicAdd(&g[2 * i + 1], v >> 16);
+    }
+}
+
+// One workgroup per Block, a thread = one byte value: the sampled bytes of every (pos, prev) cell, then per candidate the
+// thread's part of sum c * L(c) and of the used cells (xzamd_ll_byte over its column of the table), summed over the
+// workgroup; thread 0 prices the candidates and applies the rule.  props[b] = lc | lp << 8.
+__global__ __launch_bounds__(256) void k_lclp_choose(const uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t lc, uint32_t lp,
+        uint32_t* __restrict__ props)
+{
+    __shared__ uint32_t cells[XZAMD_LL_CELLS];
+    __shared__ unsigned long long part_cl[4];
+    __shared__ uint32_t part_used[4];
+    __shared__ unsigned long long S[XZAMD_LL_MAXCAND];
+    const uint32_t blk = blockIdx.x, t = threadIdx.x;
+    if (blk >= nblocks) return;
+    uint32_t cand[XZAMD_LL_MAXCAND];
+    const uint32_t ncand = xzamd_ll_cands(lc, lp, cand);
+    if (ncand == 1) {
+        if (t == 0) props[blk] = cand[0];
+        return;
+    }
+    const uint32_t* __restrict__ g = hist + (uint64_t)blk * XZAMD_LL_HIST_WORDS;
+    {   // four threads per cell, 64 byte values each
+        const uint32_t* __restrict__ row = g + (t >> 2) * 256u + (t & 3u) * 64u;
+        uint32_t s = 0;
+        for (uint32_t v = 0; v < 64; ++v) s += row[v];
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        if ((t & 3u) == 0) cells[t >> 2] = s;
+    }
+    __syncthreads();
+    for (uint32_t k = 0; k < ncand; ++k) {
+        uint64_t cl = 0;
+        uint32_t used = 0;
+        xzamd_ll_byte(g + t, 256, cand[k] & 255u, cand[k] >> 8, AD_LOG, &cl, &used);
+        for (int s = 32; s > 0; s >>= 1) {
+            cl += __shfl_xor((unsigned long long)cl, s);
+            used += __shfl_xor(used, s);
+        }
+        if ((t & 63u) == 0) { part_cl[t >> 6] = cl; part_used[t >> 6] = used; }
+        __syncthreads();
+        if (t == 0)
+            S[k] = xzamd_ll_cost(xzamd_ll_ctx(cells, cand[k] & 255u, cand[k] >> 8, AD_LOG),
+                    part_cl[0] + part_cl[1] + part_cl[2] + part_cl[3], part_used[0] + part_used[1] + part_used[2] + part_used[3]);
+        __syncthreads();
+    }
+    if (t == 0) {
+        uint64_t Ns = 0, Sk[XZAMD_LL_MAXCAND];
+        for (uint32_t i = 0; i < XZAMD_LL_CELLS; ++i) Ns += cells[i];
+        for (uint32_t k = 0; k < ncand; ++k) Sk[k] = S[k];
+        props[blk] = cand[xzamd_ll_rule(Sk, cand, ncand, Ns)];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // SHA-256 Block check (check/sha256.c:120-189, FIPS 180-4): a serial hash per Block, so one THREAD per
 // Block (Blocks are the parallelism; the default Check, CRC64, stays the fast path).  32 bytes per Block.
 // ------------------------------------------------------------------------------------------
@@ -876,6 +991,40 @@ int xzk_bcj_blocks(const uint8_t* d_in, uint8_t* d_out, uint32_t n, uint32_t blo
     hipLaunchKernelGGL(k_arm64_bcj, dim3(grid_for((uint64_t)n / 4 + 1, 256, 65536)), dim3(256), 0, st, d_in, d_out, n, block_size, nblocks,
             d_kind);
     return (int)hipGetLastError();
+}
+
+int xzk_lclp_stats(const uint8_t* d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t* d_hist, void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    if (nblocks == 0) return 0;
+    if (block_size == 0 || (uint64_t)nblocks * block_size < n) return (int)hipErrorInvalidValue;
+    int e = (int)hipMemsetAsync(d_hist, 0, (uint64_t)nblocks * XZAMD_LL_HIST_WORDS * 4, st);
+    if (e || n == 0) return e;
+    const uint32_t wpb = (block_size + XZAMD_AD_PERIOD - 1) / XZAMD_AD_PERIOD;     // sample windows per full Block
+    const uint32_t rpb = (wpb + LL_RUN - 1) / LL_RUN;
+    const uint64_t grid = (uint64_t)rpb * nblocks;
+    if (grid > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_lclp_stats, dim3((uint32_t)grid), dim3(256), 0, st, d_in, n, block_size, rpb, d_hist);
+    return (int)hipGetLastError();
+}
+
+int xzk_lclp_choose(const uint32_t* d_hist, uint32_t nblocks, uint32_t lc, uint32_t lp, uint32_t* d_props, void* stream_)
+{
+    if (nblocks == 0) return 0;
+    if (lc > 4 || lp > 4 || lc + lp > 4) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_lclp_choose, dim3(nblocks), dim3(256), 0, (hipStream_t)stream_, d_hist, nblocks, lc, lp, d_props);
+    return (int)hipGetLastError();
+}
+
+int xzk_lclp_read(const uint32_t* d_hist, const uint32_t* d_props, uint32_t nblocks, uint32_t* h_hist, uint32_t* h_props, void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    int e = 0;
+    if (nblocks == 0) return 0;
+    if (h_hist) e = (int)hipMemcpyAsync(h_hist, d_hist, (uint64_t)nblocks * XZAMD_LL_HIST_WORDS * 4, hipMemcpyDeviceToHost, st);
+    if (!e && h_props) e = (int)hipMemcpyAsync(h_props, d_props, (uint64_t)nblocks * 4, hipMemcpyDeviceToHost, st);
+    if (!e) e = (int)hipStreamSynchronize(st);
+    return e;
 }
 
 int xzk_sha256_blocks(const uint8_t* d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint8_t* d_out32, void* stream_)

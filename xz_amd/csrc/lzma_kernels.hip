@@ -171,6 +171,18 @@ struct Lz {
     uint32_t* gp;                             // parse pieces (PG): every other probability of the piece's model, u32 each, global
 };
 
+// lc / lp of Block blk: the job's, or with a props table (XZAMD_F_AUTO_LCLP) the Block's own pair -- never more literal
+// coders than the job's, so every slot stride (0x300 << (a.lc + a.lp), model_slots_pad) stays the job's and such a Block
+// uses the front of its slots.  blk is wave-uniform; callers load once at kernel start.
+__device__ __forceinline__ void block_lclp(const xzamd_span_args& a, uint32_t blk, uint32_t& lc, uint32_t& lp)
+{
+    lc = a.lc; lp = a.lp;
+    if (a.props_tab != nullptr) {
+        const uint32_t v = uni(a.props_tab[blk]);
+        lc = v & 255u; lp = v >> 8;
+    }
+}
+
 __device__ __forceinline__ uint32_t dist_slot_of(uint32_t d)
 {
     if (d <= 4) return d;
@@ -1392,7 +1404,7 @@ __device__ __forceinline__ void span_encode_one(const xzamd_span_args& a, const 
     }
 
     Lz z;
-    z.lc = a.lc; z.lp = a.lp; z.pb = a.pb;
+    block_lclp(a, blk, z.lc, z.lp); z.pb = a.pb;
     z.cnt_len = z.cnt_match = z.cnt_align = 0;
     const uint32_t lit_size = 0x300u << (a.lc + a.lp);       // literal coders of this span (lc + lp <= 4)
     z.lit = reinterpret_cast<plit_t*>(a.lit) + (uint64_t)span * lit_size;
@@ -1681,7 +1693,7 @@ __device__ __forceinline__ void span_encode_one(const xzamd_span_args& a, const 
             hdr[2] = (uint8_t)(usize - 1);
             hdr[3] = (uint8_t)((csize - 1) >> 8);
             hdr[4] = (uint8_t)(csize - 1);
-            if (need_props) hdr[5] = (uint8_t)((a.pb * 5 + a.lp) * 9 + a.lc);
+            if (need_props) hdr[5] = (uint8_t)((a.pb * 5 + z.lp) * 9 + z.lc);
         }
         need_props = false; need_dict_reset = false; need_state_reset = false;
         out_off += hl + csize;
@@ -1848,7 +1860,7 @@ __device__ __forceinline__ void parse_piece_one(const xzamd_span_args& a, const 
     // pb = 3, 4: the piece's price model -- which is the parser's alone, the coder keeps its own (k_model_syms, the real
     // pb) -- takes a pb = 2 view of the positions; the bit-price and length tables of the window cover four position
     // states (oracle: parse_block).  The recorded symbols are valid under any pb.
-    z.lc = a.lc; z.lp = a.lp; z.pb = a.pb < 2u ? a.pb : 2u;
+    block_lclp(a, blk, z.lc, z.lp); z.pb = a.pb < 2u ? a.pb : 2u;
     z.cnt_len = z.cnt_match = z.cnt_align = 0;
     const uint32_t lit_size = 0x300u << (a.lc + a.lp);
     z.lit = reinterpret_cast<plit_t*>(a.lit) + (uint64_t)span * lit_size;
@@ -2266,7 +2278,7 @@ __global__ __launch_bounds__(64) void k_model_walk(xzamd_span_args a, uint32_t n
     const uint32_t* __restrict__ pinfo = a.pinfo + (uint64_t)blk * a.max_spb * XZAMD_PINFO_WORDS + (SUB ? 0u : XZAMD_PINFO_WORDS / 2);
 
     Lz z;
-    z.lc = a.lc; z.lp = a.lp; z.pb = SUB ? min(a.pb, 2u) : a.pb;     // (the snapshots are the PARSER's price model: its pb view)
+    block_lclp(a, blk, z.lc, z.lp); z.pb = SUB ? min(a.pb, 2u) : a.pb;     // (the snapshots are the PARSER's price model: its pb view)
     z.cnt_len = z.cnt_match = z.cnt_align = 0;
     z.lit = LITG ? reinterpret_cast<plit_t*>(litw) : nullptr;
     z.gp = nullptr;
@@ -2591,7 +2603,11 @@ __global__ __launch_bounds__(256) void k_resume_export(xzamd_span_args a, uint32
         uint32_t w = sr[t < 3 ? 0u : t - 3u];                       // t = 3 .. 7: state, rep distances
         if (t == 0) w = block0 + blk;
         if (t == 1) w = a.enc_tab[2 * slot] - blk * a.block_size;
-        if (t == 2) w = a.lc | a.lp << 8 | a.pb << 16 | kind << 24;
+        if (t == 2) {
+            uint32_t lc, lp;                                        // (the Block's own pair: what a decoder resumes with)
+            block_lclp(a, blk, lc, lp);
+            w = lc | lp << 8 | a.pb << 16 | kind << 24;
+        }
         reinterpret_cast<uint32_t*>(rec)[t] = w;
     }
     const uint4* __restrict__ src = reinterpret_cast<const uint4*>(a.cb_start + (uint64_t)slot * a.model_slots_pad);
@@ -2682,7 +2698,11 @@ __global__ __launch_bounds__(64) void k_rc_chunks(xzamd_span_args a, uint32_t nc
     hdr[2] = (uint8_t)(c.usize - 1);
     hdr[3] = (uint8_t)((csize - 1) >> 8);
     hdr[4] = (uint8_t)(csize - 1);
-    if (c.flags & XZAMD_CH_PROPS) hdr[5] = (uint8_t)((a.pb * 5 + a.lp) * 9 + a.lc);
+    if (c.flags & XZAMD_CH_PROPS) {
+        // (a lane per chunk: the Block of the chunk, hence its pair, differs from lane to lane)
+        const uint32_t pr = a.props_tab != nullptr ? a.props_tab[c.in_start / a.block_size] : (a.lc | a.lp << 8);
+        hdr[5] = (uint8_t)((a.pb * 5 + (pr >> 8)) * 9 + (pr & 255u));
+    }
     a.chunks[idx].csize = hl + csize;
     if ((csize > 65536u || csize >= cap) && a.err) atomicCAS(a.err, 0u, 4u);      // the price sum was far off: cannot happen
 }

@@ -14,6 +14,7 @@
 #include "xzamd_internal.h"
 #include "delta_rule.h"
 #include "auto_bcj_rule.h"
+#include "lclp_rule.h"
 
 #include <stdio.h>
 #include <pthread.h>
@@ -82,6 +83,7 @@ typedef struct {
 	int auto_delta;
 	uint32_t hs_bcj;             /* XZAMD_F_AUTO_BCJ: header size of a Block that got a BCJ filter (x86 and ARM64 take the same two bytes of Filter Flags) */
 	int auto_bcj;
+	int auto_lclp;               /* XZAMD_F_AUTO_LCLP: every Block is parsed and coded with the lc / lp chosen for it (span args: props_tab) */
 	int segments;                  /* XZAMD_F_SEGMENTS: per Block only its chunk chain */
 	xzamd_mode m;
 	call_knobs k;
@@ -125,6 +127,7 @@ struct xzamd_ctx {
 	dbuf sym_len[2], sym_dist[2], prior, enc_tab[2], enc_cnt[2];   /* two-phase mode ([2]: one set per pipeline parity) */
 	dbuf tok, chunks, h_chunks;                                    /* coder of the two-phase mode: tokens, chunk table */
 	dbuf dhist, ddist[2];                                          /* XZAMD_F_AUTO_DELTA: histograms of the batch, chosen distance per Block (per pipeline parity) */
+	dbuf lhist, dprops[2];                                         /* XZAMD_F_AUTO_LCLP: joint histograms of the batch, chosen lc | lp << 8 per Block (per pipeline parity) */
 	dbuf bhist, bkind[2];                                          /* XZAMD_F_AUTO_BCJ: histograms of the batch with the site counts behind them, chosen filter id per Block (per pipeline parity) */
 	dbuf resume_sr;                                                /* what the token walk of every encode span started from (resume table asked for) */
 	/* The resume table of the last encode with XZAMD_F_KEEP_RESUME / _VERIFY (kernels_api.h), kept until the next encode;
@@ -256,19 +259,19 @@ static void ctx_device_bufs(xzamd_ctx *c, dbuf **d, size_t *nd)
 {
 	dbuf *all[] = { &c->keys_a, &c->keys_b, &c->vals_a, &c->vals_b, &c->rank, &c->sorted_pos,
 		&c->prev2, &c->prev3, &c->prev4, &c->prev8, &c->prev16, &c->prev24, &c->prev32, &c->key64_a, &c->key64_b, &c->sa, &c->sa_rank, &c->sort_tmp,
-		&c->scratch, &c->litp, &c->mlen, &c->mdist, &c->bcj[0], &c->bcj[1], &c->bcjt, &c->est, &c->mtop, &c->order, &c->dhist, &c->bhist,
+		&c->scratch, &c->litp, &c->mlen, &c->mdist, &c->bcj[0], &c->bcj[1], &c->bcjt, &c->est, &c->mtop, &c->order, &c->dhist, &c->bhist, &c->lhist,
 		&c->sym_len[0], &c->sym_len[1], &c->sym_dist[0], &c->sym_dist[1], &c->tok, &c->cb_log[0], &c->cb_log[1],
 		/* small ones */
 		&c->chunks,
 		&c->span_bytes, &c->strip_crc, &c->block_crc, &c->segs, &c->lits, &c->trace, &c->errw, &c->errw2,
 		&c->totals, &c->span_tab[0], &c->span_tab[1], &c->span_cnt[0], &c->span_cnt[1], &c->prior, &c->enc_tab[0], &c->enc_tab[1], &c->enc_cnt[0], &c->enc_cnt[1],
 		&c->pinfo[0], &c->pinfo[1], &c->snap_sr, &c->part_tab, &c->cb_bnd[0], &c->cb_bnd[1], &c->cb_hdr[0], &c->cb_hdr[1], &c->cb_start[0], &c->cb_start[1],
-		&c->cb_carry[0], &c->cb_carry[1], &c->resume_sr, &c->ddist[0], &c->ddist[1], &c->bkind[0], &c->bkind[1] };
+		&c->cb_carry[0], &c->cb_carry[1], &c->resume_sr, &c->ddist[0], &c->ddist[1], &c->bkind[0], &c->bkind[1], &c->dprops[0], &c->dprops[1] };
 	_Static_assert(sizeof(all) / sizeof(all[0]) <= CTX_NBUF_MAX, "ctx_device_bufs: raise CTX_NBUF_MAX");
 	*nd = sizeof(all) / sizeof(all[0]);
 	memcpy(d, all, sizeof(all));
 }
-#define CTX_NBIG 37      /* the first CTX_NBIG entries of ctx_device_bufs scale with the batch */
+#define CTX_NBIG 38      /* the first CTX_NBIG entries of ctx_device_bufs scale with the batch */
 
 void xzamd_ctx_destroy(xzamd_ctx *c)
 {
@@ -406,6 +409,13 @@ extern int xzk_bcj_choose(const uint32_t *d_hist, const uint32_t *d_nsites, uint
 		uint32_t *d_kind, uint32_t *d_dist, void *stream) __attribute__((weak));
 extern int xzk_bcj_blocks(const uint8_t *d_in, uint8_t *d_out, uint32_t n, uint32_t block_size, uint32_t nblocks, const uint32_t *d_kind,
 		int copy, void *stream) __attribute__((weak));
+/* ... and of the automatic literal context: without them XZAMD_F_AUTO_LCLP is XZAMD_OPTIONS_ERROR */
+extern int xzk_lclp_stats(const uint8_t *d_in, uint32_t n, uint32_t block_size, uint32_t nblocks, uint32_t *d_hist, void *stream)
+		__attribute__((weak));
+extern int xzk_lclp_choose(const uint32_t *d_hist, uint32_t nblocks, uint32_t lc, uint32_t lp, uint32_t *d_props, void *stream)
+		__attribute__((weak));
+extern int xzk_lclp_read(const uint32_t *d_hist, const uint32_t *d_props, uint32_t nblocks, uint32_t *h_hist, uint32_t *h_props,
+		void *stream) __attribute__((weak));
 xzamd_repair_report *xzamd_ctx_repair_report_(xzamd_ctx *c) { return &c->repair; }
 /* A repair re-encodes Blocks on the context of the call it repairs: the kept table leaves the context meanwhile (the
  * re-encode would free it), the stats of the repaired call come back afterwards */
@@ -457,6 +467,17 @@ int xzamd_debug_fetch(xzamd_ctx *c, int what, void *out, uint64_t bytes)
 			: what == XZAMD_DEBUG_CB_HDR ? &c->cb_hdr[1] : what == XZAMD_DEBUG_CB_START ? &c->cb_start[1]
 			: what == XZAMD_DEBUG_DELTA_HIST ? &c->dhist : what == XZAMD_DEBUG_DELTA_DIST ? &c->ddist[c->last_par]
 			: what == XZAMD_DEBUG_BCJ_HIST ? &c->bhist : what == XZAMD_DEBUG_BCJ_KIND ? &c->bkind[c->last_par] : NULL;
+	if (what == XZAMD_DEBUG_LCLP_HIST || what == XZAMD_DEBUG_LCLP_PROPS) {
+		/* the statistic and the choices of the last batch, through the kernel layer's own read-back */
+		const int hist = what == XZAMD_DEBUG_LCLP_HIST;
+		const dbuf *l = hist ? &c->lhist : &c->dprops[c->last_par];
+		const uint64_t per = hist ? 4ull * XZAMD_LL_HIST_WORDS : 4ull;
+		if (!xzk_lclp_read || !l->p || l->cap < bytes || bytes % per)
+			return XZAMD_PROG_ERROR;
+		xzk_set_device(c->device);
+		return xzk_lclp_read(hist ? (const uint32_t *)l->p : NULL, hist ? NULL : (const uint32_t *)l->p, (uint32_t)(bytes / per),
+				hist ? (uint32_t *)out : NULL, hist ? NULL : (uint32_t *)out, c->own_stream) ? XZAMD_DEVICE_ERROR : XZAMD_OK;
+	}
 	if (!b || !b->p || b->cap < bytes)
 		return XZAMD_PROG_ERROR;
 	xzk_set_device(c->device);
@@ -583,6 +604,14 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		if (flags & XZAMD_F_REPAIR)
 			return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: not with XZAMD_F_REPAIR (the repair plans Block Headers from one chain)", 0);
 	}
+	if (flags & XZAMD_F_AUTO_LCLP) {
+		if (!xzk_lclp_stats || !xzk_lclp_choose)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto lclp: this build has no kernels for it", 0);
+		if (flags & XZAMD_F_SEGMENTS)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto lclp: Blocks only, not the chunk chains of XZAMD_F_SEGMENTS", 0);
+		if (flags & XZAMD_F_REPAIR)
+			return fail(c, XZAMD_OPTIONS_ERROR, "auto lclp: not with XZAMD_F_REPAIR (the repair re-encodes Blocks with the job's lc / lp)", 0);
+	}
 	if (chains && (!(flags & XZAMD_F_SEGMENTS) || !xzamd_chains_encoded_))
 		return fail(c, XZAMD_OPTIONS_ERROR, "chains: this build has no unit for bare chunk chains", 0);
 	if ((flags & XZAMD_F_REPAIR) && (flags & XZAMD_F_SEGMENTS) && !chains)
@@ -647,6 +676,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 		double per_byte = xzamd_work_bytes_per_byte_(opt);
 		if (flags & XZAMD_F_AUTO_DELTA) per_byte += xzamd_auto_delta_bytes_per_byte_(block_size);
 		if (flags & XZAMD_F_AUTO_BCJ) per_byte += xzamd_auto_bcj_bytes_per_byte_(block_size, (flags & XZAMD_F_AUTO_DELTA) != 0);
+		if (flags & XZAMD_F_AUTO_LCLP) per_byte += xzamd_auto_lclp_bytes_per_byte_(block_size);
 		/* the resume table (only when asked for): one record per encode-span slot, for the whole call */
 		if ((flags & (XZAMD_F_KEEP_RESUME | XZAMD_F_VERIFY)) && J->m.two)
 			per_byte += (double)(XZAMD_RESUME_BYTES(J->m.model_slots) + 32u) * (double)(block_size / XZAMD_ENC_MIN_LEN + 1) / (double)block_size;
@@ -674,6 +704,7 @@ static int call_setup(xzamd_ctx *c, job_env *J, const uint8_t *d_in, uint64_t in
 	J->filtered = opt->bcj != 0;          /* any filter in front of LZMA2: the encoder reads a filtered copy */
 	J->auto_delta = (flags & XZAMD_F_AUTO_DELTA) != 0;     /* ... or the copy in which every Block has the filter chosen for it */
 	J->auto_bcj = (flags & XZAMD_F_AUTO_BCJ) != 0;
+	J->auto_lclp = (flags & XZAMD_F_AUTO_LCLP) != 0;
 	/* Two-stream pipeline (two-phase mode): the back end of batch i -- range coder, checks, sizes, gather -- runs on the
 	 * second stream while the front end of batch i + 1 -- match structures, plan, parse -- runs on the caller's: the coder
 	 * is a few thousand latency-bound wavefronts, the structure build is HBM-bound, they share the GPU well.  The
@@ -906,6 +937,10 @@ static int batch_reserve(xzamd_ctx *c, const job_env *J, const batch_run *B, int
 		NEED(ddist[par], 4 * nb, 0);
 		NEED(h_ddist[par], 4 * nb + 16, 1);
 	}
+	if (J->auto_lclp) {
+		NEED(lhist, 4ull * XZAMD_LL_HIST_WORDS * nb, 0);
+		NEED(dprops[par], 4 * nb, 0);
+	}
 	if (opt->bcj2) NEED(bcjt, n + 16, 0);
 #undef NEED
 	return r;
@@ -944,6 +979,7 @@ static void span_args_init(const xzamd_ctx *c, const job_env *J, const batch_run
 	a->depth = opt->gpu_depth;
 	a->hash_bytes = J->hb;
 	a->lc = opt->lc; a->lp = opt->lp; a->pb = opt->pb;
+	a->props_tab = J->auto_lclp ? (const uint32_t *)c->dprops[par].p : NULL;      /* (this batch's parity: front end and coder alike) */
 	if (J->m.two) {
 		a->sym_len = (uint16_t *)c->sym_len[par].p;
 		a->sym_dist = (uint32_t *)c->sym_dist[par].p;
@@ -1408,6 +1444,14 @@ static int front_input(xzamd_ctx *c, const job_env *J, batch_run *B, void *st)
 		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic per-Block filter", e);
 		B->enc_in = X;
 	}
+	if (J->auto_lclp) {
+		/* the literal context of every Block, from the bytes LZMA2 will code -- behind the filter stage above -- and in stream
+		 * order in front of the parse and the coder, which read the table through the span arguments; the host never
+		 * needs it (the pair travels in the chunks' properties bytes, not in the Block Header) */
+		int e = xzk_lclp_stats(B->enc_in, n, bs, nb, (uint32_t *)c->lhist.p, st);
+		if (!e) e = xzk_lclp_choose((const uint32_t *)c->lhist.p, nb, J->opt->lc, J->opt->lp, (uint32_t *)c->dprops[B->par].p, st);
+		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic literal context", e);
+	}
 	return XZAMD_OK;
 }
 
@@ -1677,6 +1721,8 @@ int xzamd_stream_encode_device(xzamd_ctx *c,
 		return fail(c, XZAMD_OPTIONS_ERROR, "auto delta: Blocks only -- the single Block of XZAMD_F_SINGLE has one chain", 0);
 	if (c && (flags & XZAMD_F_SINGLE) && (flags & XZAMD_F_AUTO_BCJ))
 		return fail(c, XZAMD_OPTIONS_ERROR, "auto bcj: Blocks only -- the single Block of XZAMD_F_SINGLE has one chain", 0);
+	if (c && (flags & XZAMD_F_SINGLE) && (flags & XZAMD_F_AUTO_LCLP))
+		return fail(c, XZAMD_OPTIONS_ERROR, "auto lclp: Blocks only, not the single Block of XZAMD_F_SINGLE", 0);
 	if (c && (flags & XZAMD_F_SINGLE)) {
 		if (!xzamd_single_encode_)
 			return fail(c, XZAMD_OPTIONS_ERROR, "single: this build has no unit for bare chunk chains", 0);
@@ -1762,6 +1808,47 @@ int xzamd_auto_bcj_device(xzamd_ctx *c, const void *d_in_, uint64_t in_size, uin
 		if (!e) e = xzk_d2h(kind_out + b0, c->bkind[0].p, 4ull * nb, st);
 		if (!e) e = xzk_sync(st);
 		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic bcj analysis", e);
+	}
+	return XZAMD_OK;
+}
+
+/* The analysis of XZAMD_F_AUTO_LCLP on its own, in the same form: props_out[b] = lc | lp << 8 for a job with (lc, lp) */
+int xzamd_auto_lclp_device(xzamd_ctx *c, const void *d_in_, uint64_t in_size, uint64_t block_size, uint32_t lc, uint32_t lp,
+		uint32_t *props_out, uint64_t cap, uint64_t *nblocks_out, void *stream)
+{
+	if (!c || (!d_in_ && in_size) || !nblocks_out || (!props_out && cap))
+		return XZAMD_PROG_ERROR;
+	c->err[0] = 0;
+	if (!xzk_lclp_stats || !xzk_lclp_choose)
+		return fail(c, XZAMD_OPTIONS_ERROR, "auto lclp: this build has no kernels for it", 0);
+	if (block_size == 0 || block_size >= (1ull << 31))
+		return fail(c, XZAMD_OPTIONS_ERROR, "block_size must be 1 .. 2 GiB - 1", 0);
+	if (lc > 4 || lp > 4 || lc + lp > 4)
+		return fail(c, XZAMD_OPTIONS_ERROR, "lc + lp must be at most 4", 0);
+	const uint64_t total = (in_size + block_size - 1) / block_size;
+	*nblocks_out = total;
+	if (total > cap)
+		return fail(c, XZAMD_BUF_ERROR, "props_out too small", 0);
+	if (c->pend.active)
+		(void)pend_complete(c);      /* (its result is the deferred call's) */
+	void *st = stream ? stream : c->own_stream;
+	int e = xzk_set_device(c->device);
+	if (e) return fail(c, XZAMD_DEVICE_ERROR, "hipSetDevice", e);
+	uint64_t max_blocks = ((1ull << 31) - 1) / block_size;
+	if (max_blocks > (1u << 12)) max_blocks = 1u << 12;      /* (64 KiB of histograms per Block) */
+	c->last_par = 0;
+	for (uint64_t b0 = 0; b0 < total; b0 += max_blocks) {
+		const uint64_t nb = total - b0 < max_blocks ? total - b0 : max_blocks;
+		const uint64_t off = b0 * block_size;
+		const uint64_t n = in_size - off < nb * block_size ? in_size - off : nb * block_size;
+		int r = dgrow(c, &c->lhist, 4ull * XZAMD_LL_HIST_WORDS * nb, 0);
+		if (!r) r = dgrow(c, &c->dprops[0], 4 * nb, 0);
+		if (r) return r;
+		e = xzk_lclp_stats((const uint8_t *)d_in_ + off, (uint32_t)n, (uint32_t)block_size, (uint32_t)nb, (uint32_t *)c->lhist.p, st);
+		if (!e) e = xzk_lclp_choose((const uint32_t *)c->lhist.p, (uint32_t)nb, lc, lp, (uint32_t *)c->dprops[0].p, st);
+		if (!e) e = xzk_d2h(props_out + b0, c->dprops[0].p, 4ull * nb, st);
+		if (!e) e = xzk_sync(st);
+		if (e) return fail(c, XZAMD_DEVICE_ERROR, "automatic literal context analysis", e);
 	}
 	return XZAMD_OK;
 }

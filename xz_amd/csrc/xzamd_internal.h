@@ -187,6 +187,7 @@ int xzamd_repair_knob_rung2_(void);
 double xzamd_work_bytes_per_byte_(const xzamd_lzma_options *opt);   /* device work buffers per input byte of a batch */
 double xzamd_auto_delta_bytes_per_byte_(uint64_t block_size);       /* ... what XZAMD_F_AUTO_DELTA adds to them */
 double xzamd_auto_bcj_bytes_per_byte_(uint64_t block_size, int with_auto_delta);      /* ... and XZAMD_F_AUTO_BCJ */
+double xzamd_auto_lclp_bytes_per_byte_(uint64_t block_size);        /* ... and XZAMD_F_AUTO_LCLP */
 
 /* Shared by the host units only.  The version script exports every xzamd_* name; these stay inside the library. */
 #define XZAMD_HIDDEN __attribute__((visibility("hidden")))

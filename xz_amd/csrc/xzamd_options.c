@@ -6,6 +6,7 @@
 #include "xzamd_internal.h"
 #include "delta_rule.h"
 #include "auto_bcj_rule.h"
+#include "lclp_rule.h"
 
 #include <string.h>
 
@@ -164,4 +165,11 @@ double xzamd_auto_delta_bytes_per_byte_(uint64_t block_size)
 double xzamd_auto_bcj_bytes_per_byte_(uint64_t block_size, int with_auto_delta)
 {
 	return (with_auto_delta ? 0.0 : 2.0) + 4.0 * (XZAMD_AB_HIST_WORDS + XZAMD_AB_NCAND) / (double)(block_size ? block_size : 1);
+}
+
+/* What XZAMD_F_AUTO_LCLP adds: the joint histogram of every Block and its entry of the props table (one per pipeline parity).
+ * No copy of the input, and no literal-coder or model buffer grows: a Block never gets more literal coders than the job's. */
+double xzamd_auto_lclp_bytes_per_byte_(uint64_t block_size)
+{
+	return (4.0 * XZAMD_LL_HIST_WORDS + 8.0) / (double)(block_size ? block_size : 1);
 }

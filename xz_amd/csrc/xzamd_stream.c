@@ -141,6 +141,7 @@ struct lzma_internal_s {
 	int repair;                  /* XZAMD_REPAIR=1 (read at init): every job runs with XZAMD_F_REPAIR -- on its Blocks, or in single mode on
 	                              * the chains of its segments -- and is finished before the next one is launched */
 	int auto_bcj;                /* XZAMD_AUTO_BCJ=1 (read at init), likewise: every such job runs with XZAMD_F_AUTO_BCJ */
+	int auto_lclp;               /* XZAMD_AUTO_LCLP=1 (read at init): every Block job runs with XZAMD_F_AUTO_LCLP, whatever filters its chain has */
 	int auto_delta;              /* XZAMD_AUTO_DELTA=1 (read at init) on the plain chain {LZMA2}: every job runs with XZAMD_F_AUTO_DELTA */
 };
 
@@ -354,7 +355,8 @@ static lzma_ret job_launch(lzma_internal *in, devslot *d, job *j, int io, int *r
 		*rc_out = xzamd_encode_device_(d->ctx, b->d_in, n, in->block_size, &j->opt, in->check,
 				in->single ? (in->repair ? XZAMD_F_SEGMENTS | XZAMD_F_CHAINS_ | XZAMD_F_REPAIR : XZAMD_F_SEGMENTS) : in->repair ? XZAMD_F_BLOCKS_ONLY | XZAMD_F_REPAIR
 						: j->opt.bcj == 0 ? XZAMD_F_BLOCKS_ONLY | (in->auto_delta ? XZAMD_F_AUTO_DELTA : 0u) | (in->auto_bcj ? XZAMD_F_AUTO_BCJ : 0u)
-						: XZAMD_F_BLOCKS_ONLY,
+								| (in->auto_lclp ? XZAMD_F_AUTO_LCLP : 0u)
+						: XZAMD_F_BLOCKS_ONLY | (in->auto_lclp ? XZAMD_F_AUTO_LCLP : 0u),
 				b->d_out, b->d_out_cap, out_size, j->binfo, j->binfo_cap,
 				&j->nblocks, NULL, ((nd && *nd == '1') || in->repair) ? NULL : deferred);
 	return LZMA_OK;
@@ -697,6 +699,9 @@ static lzma_ret encoder_init(lzma_stream *strm, lzma_ret r, const xzamd_lzma_opt
 		/* XZAMD_AUTO_BCJ=1: the per-Block BCJ filter, with the same exclusions */
 		const char *ab = getenv("XZAMD_AUTO_BCJ");
 		in->auto_bcj = ab && *ab == '1' && !single && !in->repair;
+		/* XZAMD_AUTO_LCLP=1: the per-Block literal context (lc / lp); ignored in the single-Block encoder and for repaired jobs */
+		const char *al = getenv("XZAMD_AUTO_LCLP");
+		in->auto_lclp = al && *al == '1' && !single && !in->repair;
 	}
 	in->sequence = ISEQ_RUN;
 	in->sseq = SEQ_HEADER;
